@@ -14,10 +14,23 @@ eager step with the bucketed overlapped gradient sync.
 Protocol (driver contract): --warmup untimed steps, then exactly --steps
 timed steps bracketed by barrier + torch.cuda.synchronize() on both sides;
 elapsed is MAX over ranks; rank 0 prints ONE json line.
+
+A plain run does only that.  --dump-outputs DIR additionally shows what the
+timed path computes, reproducibly: after the timed steps the model, optimizer
+and RNG state are rewound to the seeded start, the timed path (the same
+captured graph) runs one further, untimed step on the first batch, and that
+step's loss and resulting model state are written as DIR/<name>.npy.  The
+rewind is what makes two runs, or two builds, comparable output for output:
+the kernels accumulate with fp32 atomics, a ~1e-7 per-step difference that
+lr=0.1 training amplifies into the leading digits within tens of steps, so
+the state reached after the timed steps themselves is not repeatable.
+--full adds the secondary measurements after the timed steps: checkpoint
+save/restore seconds and the multi-GB checkpoint round-trip.
 """
 from __future__ import annotations
 
 import argparse
+import copy
 import json
 import os
 import sys
@@ -120,6 +133,66 @@ def measure_large_checkpoint(folder: str, gib: float = 2.0):
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # well inside the 64 MB cap for --dump-outputs
+
+
+def snapshot_state(modules: dict, optims: list) -> dict:
+    """Private copy of everything a training step reads and mutates: module
+    and optimizer state (state_dict() hands out live tensors, hence the deep
+    copy) and the RNG streams.  ``modules`` is {prefix: module}."""
+    snap = {
+        "modules": {k: copy.deepcopy(m.state_dict()) for k, m in modules.items()},
+        "optims": [copy.deepcopy(o.state_dict()) for o in optims],
+        "rng": torch.get_rng_state(),
+        "cuda_rng": None,
+    }
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+        snap["cuda_rng"] = torch.cuda.get_rng_state()
+    return snap
+
+
+def restore_state(snap: dict, modules: dict, optims: list) -> None:
+    """Rewind to ``snap`` in place (parameter storage is kept, so a captured
+    graph stays valid); modules first — the flat optimizers re-sync their
+    bf16 weight mirrors from the parameters on load."""
+    for k, m in modules.items():
+        m.load_state_dict(snap["modules"][k])
+    for o, state in zip(optims, snap["optims"]):
+        o.load_state_dict(copy.deepcopy(state))
+    torch.set_rng_state(snap["rng"])
+    if snap["cuda_rng"] is not None:
+        torch.cuda.set_rng_state(snap["cuda_rng"])
+
+
+def dump_outputs(folder: str, loss, modules: dict):
+    """Write what a step produced as ``folder/<name>.npy``: the
+    loss the step returned and the state (parameters + buffers) it left in
+    every module of ``modules`` ({prefix: module}).  Floating tensors are
+    stored as float32, integer ones as float64.  When the state exceeds
+    DUMP_BUDGET_BYTES every tensor is cut down to the same fixed, seeded
+    sample of its flattened elements, so two builds dump the same entries."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    arrays = {}
+    if loss is not None:
+        arrays["loss"] = loss.detach().float().cpu().numpy()
+    for prefix, module in modules.items():
+        for name, tensor in module.state_dict().items():
+            t = tensor.detach()
+            t = t.float() if t.is_floating_point() else t.double()
+            arrays[f"{prefix}.{name}"] = t.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    rng = np.random.RandomState(20240229)
+    for name, arr in arrays.items():
+        if keep < 1.0 and arr.size > 1:
+            n = max(1, int(arr.size * keep))
+            idx = np.sort(rng.choice(arr.size, n, replace=False))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(folder, f"{name}.npy"), arr)
+
+
 def main():
     parser = argparse.ArgumentParser("flashy_amd bench")
     parser.add_argument("--gpus", type=int, default=1)
@@ -138,8 +211,19 @@ def main():
                         help="use the torch-module model (MIOpen convs) with"
                              " our fused optimizer/loss instead of the native"
                              " NHWC kernel model")
+    parser.add_argument("--full", action="store_true",
+                        help="after the timed steps also run the secondary"
+                             " measurements (checkpoint save/restore and the"
+                             " multi-GB checkpoint round-trip); a plain run"
+                             " only times the training step")
     parser.add_argument("--no-ckpt", action="store_true",
-                        help="skip the checkpoint save/restore measurement")
+                        help="with --full: skip the checkpoint save/restore"
+                             " measurement")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps rewind to the seeded"
+                             " start, run the timed path for one more,"
+                             " untimed step and write its loss and the"
+                             " model state it left as DIR/<name>.npy")
     parser.add_argument("--channels-last", action="store_true")
     parser.add_argument("--workload", default="cifar", choices=["cifar", "gan"],
                         help="gan = DCGAN-style G/D on 64x64 synthetic images"
@@ -186,6 +270,8 @@ def main():
     else:
         optim = torch.optim.SGD(model.parameters(), lr=0.1, momentum=0.9,
                                 weight_decay=5e-4)
+    start = snapshot_state({"model": model}, [optim]) \
+        if args.dump_outputs else None
 
     # synthetic data: pinned host pool -> static device buffers each step
     pool_n = 8
@@ -298,8 +384,19 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(t.item())
 
+    if start is not None:
+        # every rank replays (the step may hold collectives); rank 0 writes
+        restore_state(start, {"model": model}, [optim])
+        static_x.copy_(xs[0], non_blocking=True)
+        static_y.copy_(ys[0], non_blocking=True)
+        loss = runner()
+        if use_cuda:
+            torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, loss, {"model": model})
+
     ckpt_save_s = ckpt_restore_s = large_ckpt = None
-    if not args.no_ckpt and rank == 0:
+    if args.full and not args.no_ckpt and rank == 0:
         ckpt_save_s, ckpt_restore_s = measure_checkpoint(model, optim, ".")
         if ws == 1:
             large_ckpt = measure_large_checkpoint(".")
@@ -370,6 +467,9 @@ def main_gan(args):
     adv = AdversarialLoss(disc, d_optim)
     batch = args.batch
     real = torch.tanh(torch.randn(batch, 3, 64, 64, device=device))
+    nets = {"generator": gen, "discriminator": disc}
+    start = snapshot_state(nets, [g_optim, d_optim]) \
+        if args.dump_outputs else None
 
     def step():
         z = torch.randn(batch, nz, 1, 1, device=device)
@@ -417,6 +517,13 @@ def main_gan(args):
     if ws > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(t.item())
+    if start is not None:
+        restore_state(start, nets, [g_optim, d_optim])
+        g_loss = step()
+        if use_cuda:
+            torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, g_loss, nets)
     if rank == 0:
         print(json.dumps({
             "metric": "img/sec", "value": ws * batch * args.steps / elapsed,

@@ -12,8 +12,21 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parent.parent
 
 
+def _hide_lone_gpu(env: dict) -> dict:
+    """Two local ranks need two GPUs once cuda is visible (RCCL refuses two
+    ranks on one device).  With fewer, hide the GPU from the child processes
+    so the ranks run the same contract over gloo on the CPU."""
+    import torch
+    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
+        env["CUDA_VISIBLE_DEVICES"] = ""
+        env["HIP_VISIBLE_DEVICES"] = ""
+    return env
+
+
 def _run(tmp: Path, *args: str) -> None:
     env = dict(os.environ)
+    if "-d" in args:
+        env = _hide_lone_gpu(env)
     env["_FLASHY_AMD_DIR"] = str(tmp)
     env["PYTHONPATH"] = str(REPO) + os.pathsep + env.get("PYTHONPATH", "")
     env.pop("RANK", None)
@@ -52,12 +65,7 @@ def test_local_ddp_two_workers(tmp_path):
 def test_bench_distributed_contract(tmp_path):
     """bench.py under torch.distributed.run exactly as the driver launches
     it (one JSON line from rank 0, value aggregated over the world)."""
-    import torch
-    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
-        pytest.skip("2 ranks need 2 GPUs once cuda is visible (RCCL "
-                    "refuses two ranks on one device); the CPU/gloo "
-                    "container covers the contract")
-    env = dict(os.environ)
+    env = _hide_lone_gpu(dict(os.environ))
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     out = subprocess.run(
