@@ -124,8 +124,8 @@ class NativeResNet(nn.Module):
         if self.stem_pool is not None:
             x = self.stem_pool(x)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-        x = x.float().mean(dim=(1, 2))      # global average pool (NHWC)
-        return self.fc(x)
+        # global average pool (NHWC) + fc as one fused head
+        return fnn.pool_linear(x, self.fc.weight, self.fc.bias)
 
     # -- weight import from the torch twin (numerics tests) ----------------
     @torch.no_grad()

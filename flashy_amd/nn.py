@@ -393,6 +393,96 @@ class Linear(nn.Module):
         return _LinearFn.apply(x, self.weight, self.bias)
 
 
+class _PoolLinearFn(torch.autograd.Function):
+    """Global average pool + small fc as ONE forward kernel and two
+    deterministic backward kernels (csrc/head.hip).  x: NHWC bf16 trunk
+    output, w [O, C] / b [O] fp32; returns fp32 logits [N, O]."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, w: torch.Tensor,
+                b: tp.Optional[torch.Tensor]):
+        x = x.contiguous()
+        N, H, W, C = x.shape
+        pooled = torch.empty((N, C), dtype=torch.float32, device=x.device)
+        y = torch.empty((N, w.shape[0]), dtype=torch.float32, device=x.device)
+        ops.pool_linear_fwd(x, w, b, pooled, y)
+        ctx.save_for_backward(pooled)
+        ctx.refs = (w, b)
+        ctx.x_shape = x.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        (pooled,) = ctx.saved_tensors
+        w, b = ctx.refs
+        dy = dy.contiguous()
+        dw = db = None
+        need_w = ctx.needs_input_grad[1]
+        need_b = b is not None and ctx.needs_input_grad[2]
+        if need_w or need_b:
+            # one kernel produces both; a frozen side is simply not written
+            dw, w_direct = _grad_target(w) if need_w else (None, True)
+            db, b_direct = _grad_target(b) if need_b else (None, True)
+            ops.head_dw(pooled, dy, dw, db)
+            dw = None if w_direct else dw
+            db = None if b_direct else db
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(ctx.x_shape, dtype=torch.bfloat16,
+                             device=dy.device)
+            ops.head_dx(dy, w, dx)
+        return dx, dw, db
+
+
+class _PoolFn(torch.autograd.Function):
+    """Global average pool, NHWC bf16 -> fp32 [N, C] (the pooling half of
+    the fused head, in front of a large rocBLAS fc)."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor):
+        x = x.contiguous()
+        N, H, W, C = x.shape
+        pooled = torch.empty((N, C), dtype=torch.float32, device=x.device)
+        ops.pool_linear_fwd(x, None, None, pooled, None)
+        ctx.x_shape = x.shape
+        return pooled
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):
+        dx = torch.empty(ctx.x_shape, dtype=torch.bfloat16, device=g.device)
+        ops.head_dx(g.contiguous(), None, dx)
+        return dx
+
+
+def pool_linear(x: torch.Tensor, weight: torch.Tensor,
+                bias: tp.Optional[torch.Tensor]) -> torch.Tensor:
+    """Classifier head ``linear(mean_hw(x))`` on an NHWC trunk output
+    ``[N, H, W, C]``; fp32 logits ``[N, O]``.  Heads below the rocBLAS
+    cutoff of :class:`Linear` run the fused pool+fc kernels; larger ones
+    the native pool kernels followed by the rocBLAS fc.  CPU falls back to
+    torch."""
+    if x.device.type != "cuda":
+        return torch.nn.functional.linear(x.float().mean(dim=(1, 2)),
+                                          weight, bias)
+    N, C = x.shape[0], x.shape[3]
+    if 2 * N * C * weight.shape[0] < _LINEAR_GEMM_CUTOFF:
+        return _PoolLinearFn.apply(x, weight, bias)
+    return _LinearFn.apply(_PoolFn.apply(x), weight, bias)
+
+
+class PoolLinearHead(nn.Module):
+    """Global average pool + :class:`Linear` over an NHWC bf16 input, run
+    through :func:`pool_linear`.  Parameters live in ``fc`` so state-dict
+    keys stay ``fc.weight`` / ``fc.bias``."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True):
+        super().__init__()
+        self.fc = Linear(in_features, out_features, bias)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return pool_linear(x, self.fc.weight, self.fc.bias)
+
+
 class _MaxPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, kernel: int, stride: int, pad: int):

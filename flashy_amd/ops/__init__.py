@@ -169,10 +169,12 @@ def _splitk_plan(M: int, ktiles: int, red_stages: int):
 def conv_fwd(x: torch.Tensor, w: torch.Tensor, y: torch.Tensor, d: ConvDims,
              relu: bool = False,
              want_stats: bool = False) -> tp.Optional[tp.Tuple[torch.Tensor, int]]:
-    """Forward conv.  With ``want_stats`` (non-split-K implicit-GEMM path
-    only) the epilogue also emits BatchNorm partials [2][K][msplit] summed
-    over each block's output rows; returns (partials, msplit) for
-    :func:`bn_finalize`, else None."""
+    """Forward conv.  With ``want_stats`` the conv also emits BatchNorm
+    partials [2][K][msplit] of its output — from the kernel epilogue
+    (single-pass implicit-GEMM kernels) or from the split-K combine, whose
+    partials are bitwise those of :func:`bn_stats` on ``y``; returns
+    (partials, msplit) for :func:`bn_finalize`, else None (the small-C stem
+    kernel emits none)."""
     ext = require()
     if d.C % 8 == 0:
         rsc = d.R * d.S * d.C
@@ -197,6 +199,18 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, y: torch.Tensor, d: ConvDims,
             ws = torch.empty(zeff * M * d.K, dtype=torch.float32, device=x.device)
             ext.conv_fwd_splitk(x.data_ptr(), w.data_ptr(), ws.data_ptr(), *d,
                                 spz, _stream())
+            if want_stats:
+                # the combine holds every output value: emit the BN partials
+                # from it instead of re-reading y in bn_stats (same msplit
+                # and summation order, so the partials are bitwise the same)
+                assert not relu, "a conv feeding BatchNorm has no fused ReLU"
+                msplit = bn_msplit(M, d.K)
+                partials = torch.empty(2 * d.K * msplit, dtype=torch.float32,
+                                       device=x.device)
+                ext.splitk_combine_stats(ws.data_ptr(), y.data_ptr(),
+                                         partials.data_ptr(), M, d.K, zeff,
+                                         msplit, _stream())
+                return partials, msplit
             ext.splitk_combine(ws.data_ptr(), y.data_ptr(), M * d.K, zeff, relu,
                                _stream())
         else:
@@ -480,3 +494,59 @@ def linear_dw(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor,
     O = dy.shape[1]
     ext.linear_dw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
                   db.data_ptr() if db is not None else 0, B, I, O, _stream())
+
+
+# ---------------------------------------------------------------------------
+# classifier head: global average pool (+ small fc) — see csrc/head.hip
+# ---------------------------------------------------------------------------
+
+def pool_linear_fwd(x: torch.Tensor, w: tp.Optional[torch.Tensor],
+                    b: tp.Optional[torch.Tensor], pooled: torch.Tensor,
+                    y: tp.Optional[torch.Tensor]) -> None:
+    """pooled[N,C] = mean over HW of NHWC bf16 ``x``; with ``w`` [O,C] also
+    y[N,O] = pooled @ w^T + b in the same kernel (``w=None``: pool only)."""
+    ext = require()
+    N, H, W, C = x.shape
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and C % 8 == 0
+    assert pooled.dtype == torch.float32 and pooled.shape == (N, C)
+    assert C * max(1, 2048 // C) * 4 <= 65536, f"C={C} exceeds the LDS row"
+    O = 0
+    if w is not None:
+        O = w.shape[0]
+        assert w.dtype == torch.float32 and w.shape == (O, C) \
+            and w.is_contiguous() and y is not None and y.shape == (N, O)
+    ext.pool_fc_fwd(x.data_ptr(), w.data_ptr() if w is not None else 0,
+                    b.data_ptr() if b is not None else 0, pooled.data_ptr(),
+                    y.data_ptr() if y is not None else 0, N, H * W, C, O,
+                    _stream())
+
+
+def head_dw(pooled: torch.Tensor, dy: torch.Tensor,
+            dw: tp.Optional[torch.Tensor],
+            db: tp.Optional[torch.Tensor]) -> None:
+    """Accumulates (+=) dw[O,C] / db[O] from dy[B,O] and the saved pooled
+    [B,C]; either target may be None (frozen).  Deterministic."""
+    B, C = pooled.shape
+    O = dy.shape[1]
+    assert dy.dtype == torch.float32 and dy.is_contiguous()
+    require().head_dw(pooled.data_ptr(), dy.data_ptr(),
+                      dw.data_ptr() if dw is not None else 0,
+                      db.data_ptr() if db is not None else 0, B, C, O,
+                      _stream())
+
+
+def head_dx(dy: torch.Tensor, w: tp.Optional[torch.Tensor],
+            dx: torch.Tensor) -> None:
+    """dx[N,H,W,C] (bf16) = (dy @ w) / HW broadcast over HW; with ``w=None``
+    ``dy`` is the fp32 [N,C] pooled gradient (plain pool backward)."""
+    N, H, W, C = dx.shape
+    assert dx.dtype == torch.bfloat16 and dx.is_contiguous() and C % 8 == 0
+    assert dy.dtype == torch.float32 and dy.is_contiguous()
+    O = 0
+    if w is not None:
+        O = w.shape[0]
+        assert w.shape == (O, C) and w.is_contiguous() and dy.shape == (N, O)
+    else:
+        assert dy.shape == (N, C)
+    require().head_dx(dy.data_ptr(), w.data_ptr() if w is not None else 0,
+                      dx.data_ptr(), N, H * W, C, O, _stream())

@@ -277,6 +277,84 @@ extern "C" void launch_splitk_combine(const void* ws, void* out, int64_t total,
         (const float*)ws, (uint16_t*)out, total, zn, relu);
 }
 
+// combine split-K fp32 partials -> bf16 AND emit the BatchNorm sum/sumsq
+// partials of the result, for a split-K forward conv that feeds a training
+// BN (saves the k_bn_stats re-read of y).  Geometry as k_bn_stats: grid
+// (K/64, msplit), 256 threads = 8 channel-octets x 32 m-lanes, each block
+// owns 64 channels x m_per_block rows.  The slices are summed in the same
+// z order as k_splitk_combine, so y is bitwise the same.  The statistics are
+// taken from the bf16-ROUNDED values, accumulated in k_bn_stats' order with
+// the same msplit, so the partials are bitwise what k_bn_stats computes from
+// y: training results do not move.  (Summing the unrounded fp32 values, as
+// the single-pass conv epilogues do, shifts the statistics by ~1e-6
+// relative, which flips bf16 roundings downstream: measured 5e-4 on the
+// flagship's first-step loss against a 1e-7 run-to-run floor.)  One partial
+// slot per block in the [2][K][msplit] layout combine_partials8 reads — no
+// atomics, no pre-zeroing.
+__global__ void __launch_bounds__(256)
+k_splitk_combine_stats(const float* __restrict__ ws, uint16_t* __restrict__ out,
+                       float* __restrict__ partials, int64_t M, int K, int zn,
+                       int msplit, int m_per_block) {
+    const int c8 = (threadIdx.x & 7) * 8;           // channel octet in group
+    const int mlane = threadIdx.x >> 3;             // 0..31
+    const int cbase = blockIdx.x * 64;
+    const int64_t m0 = (int64_t)blockIdx.y * m_per_block;
+    const int64_t m1 = min(m0 + (int64_t)m_per_block, M);
+    const int64_t slice = M * K;
+    float s[8] = {}, s2[8] = {};
+    for (int64_t m = m0 + mlane; m < m1; m += 32) {
+        const int64_t off = m * K + cbase + c8;
+        float4 a = *reinterpret_cast<const float4*>(ws + off);
+        float4 b = *reinterpret_cast<const float4*>(ws + off + 4);
+        for (int z = 1; z < zn; ++z) {
+            const float4 va = *reinterpret_cast<const float4*>(
+                ws + (int64_t)z * slice + off);
+            const float4 vb = *reinterpret_cast<const float4*>(
+                ws + (int64_t)z * slice + off + 4);
+            a.x += va.x; a.y += va.y; a.z += va.z; a.w += va.w;
+            b.x += vb.x; b.y += vb.y; b.z += vb.z; b.w += vb.w;
+        }
+        const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        short8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint16_t r = f32_to_bf16(v[j]);
+            const float vr = bf16_to_f32(r);
+            s[j] += vr;
+            s2[j] = fmaf(vr, vr, s2[j]);
+            ((uint16_t*)&o)[j] = r;
+        }
+        *reinterpret_cast<short8*>(out + off) = o;
+    }
+    // fold 32 m-lanes: LDS [2][32][64]
+    __shared__ float red[2][32][64];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        red[0][mlane][c8 + j] = s[j];
+        red[1][mlane][c8 + j] = s2[j];
+    }
+    __syncthreads();
+    const int c = threadIdx.x & 63;
+    const int which = threadIdx.x >> 6;
+    if (which < 2) {
+        float acc = 0.f;
+#pragma unroll 8
+        for (int i = 0; i < 32; ++i) acc += red[which][i][c];
+        partials[((int64_t)which * K + cbase + c) * msplit + blockIdx.y] = acc;
+    }
+}
+
+extern "C" void launch_splitk_combine_stats(const void* ws, void* out,
+                                            void* partials, int64_t M, int K,
+                                            int zn, int msplit,
+                                            hipStream_t stream) {
+    const int mpb = (int)((M + msplit - 1) / msplit);
+    dim3 grid((unsigned)(K / 64), (unsigned)msplit);
+    k_splitk_combine_stats<<<grid, 256, 0, stream>>>(
+        (const float*)ws, (uint16_t*)out, (float*)partials, M, K, zn, msplit,
+        mpb);
+}
+
 // pick (BM, BN) so the grid keeps >= ~208 workgroups (256 CUs); BN=128
 // halves the A-tile re-reads across column tiles when K allows it.
 static void pick_tile(int64_t M, int K, int* bm_out, int* bn_out) {

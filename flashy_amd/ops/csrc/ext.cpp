@@ -49,6 +49,16 @@ void launch_conv_dgrad_splitk(const void* dout, const void* w_rsck, void* ws,
                               ConvDims d, int zn, hipStream_t stream);
 void launch_splitk_combine(const void* ws, void* out, int64_t total, int zn,
                            int relu, hipStream_t stream);
+void launch_splitk_combine_stats(const void* ws, void* out, void* partials,
+                                 int64_t M, int K, int zn, int msplit,
+                                 hipStream_t stream);
+void launch_pool_fc_fwd(const void* x, const void* w, const void* b,
+                        void* pooled, void* y, int N, int HW, int C, int O,
+                        hipStream_t stream);
+void launch_head_dw(const void* pooled, const void* dy, void* dw, void* db,
+                    int B, int C, int O, hipStream_t stream);
+void launch_head_dx(const void* dy, const void* w, void* dx, int N, int HW,
+                    int C, int O, hipStream_t stream);
 void launch_weight_transpose(const void* w, void* wt, int K, int rsc,
                              hipStream_t stream);
 void launch_weight_transpose_batched(const void* src, void* dst,
@@ -251,6 +261,14 @@ PYBIND11_MODULE(_hip_ops, m) {
                                     relu ? 1 : 0, as_stream(stream));
               check_last();
           });
+    m.def("splitk_combine_stats",
+          [](uintptr_t ws, uintptr_t out, uintptr_t partials, int64_t M, int K,
+             int zn, int msplit, uintptr_t stream) {
+              launch_splitk_combine_stats((const void*)ws, (void*)out,
+                                          (void*)partials, M, K, zn, msplit,
+                                          as_stream(stream));
+              check_last();
+          });
     m.def("weight_transpose",
           [](uintptr_t w, uintptr_t wt, int K, int rsc, uintptr_t stream) {
               launch_weight_transpose((const void*)w, (void*)wt, K, rsc,
@@ -435,6 +453,31 @@ PYBIND11_MODULE(_hip_ops, m) {
              int64_t I, int64_t O, uintptr_t stream) {
               launch_linear_dw((const void*)x, (const void*)dy, (void*)dw,
                                (void*)db, B, I, O, as_stream(stream));
+              check_last();
+          });
+
+    m.def("pool_fc_fwd",
+          [](uintptr_t x, uintptr_t w, uintptr_t b, uintptr_t pooled,
+             uintptr_t y, int N, int HW, int C, int O, uintptr_t stream) {
+              launch_pool_fc_fwd((const void*)x, (const void*)w,
+                                 (const void*)b, (void*)pooled, (void*)y, N,
+                                 HW, C, O, as_stream(stream));
+              check_last();
+          });
+
+    m.def("head_dw",
+          [](uintptr_t pooled, uintptr_t dy, uintptr_t dw, uintptr_t db,
+             int B, int C, int O, uintptr_t stream) {
+              launch_head_dw((const void*)pooled, (const void*)dy, (void*)dw,
+                             (void*)db, B, C, O, as_stream(stream));
+              check_last();
+          });
+
+    m.def("head_dx",
+          [](uintptr_t dy, uintptr_t w, uintptr_t dx, int N, int HW, int C,
+             int O, uintptr_t stream) {
+              launch_head_dx((const void*)dy, (const void*)w, (void*)dx, N,
+                             HW, C, O, as_stream(stream));
               check_last();
           });
 }
