@@ -166,6 +166,22 @@ def _splitk_plan(M: int, ktiles: int, red_stages: int):
     return zn if zn >= 2 else 0
 
 
+def _underfill_zn(M: int, channels: int, stages: int) -> int:
+    """Under-fill forcing for small-M long-reduction layers (r4-class): the
+    8-wave grid of 256-row tiles underfills the chip without a K split, so
+    slice the reduction until ~160 blocks exist and the 8-wave split-K
+    launcher engages.  ``channels`` is the GEMM column count (K for fwd, C
+    for dgrad).  Returns zn (0 = leave it single pass)."""
+    if stages < 16:
+        return 0
+    bn8 = 128 if channels % 128 == 0 else 64
+    tiles8 = ((M + 255) // 256) * (channels // bn8)
+    if not tiles8 or tiles8 >= 160:
+        return 0
+    zn = min(max(2, -(-160 // tiles8)), 8, stages // 8)
+    return 0 if zn < 2 else zn
+
+
 def conv_fwd(x: torch.Tensor, w: torch.Tensor, y: torch.Tensor, d: ConvDims,
              relu: bool = False,
              want_stats: bool = False) -> tp.Optional[tp.Tuple[torch.Tensor, int]]:
@@ -181,18 +197,10 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, y: torch.Tensor, d: ConvDims,
         assert d.K % 64 == 0 and rsc % 32 == 0, d
         M = d.N * d.Ho * d.Wo
         stages = (rsc + 63) // 64
-        zn = 0 if ext.conv8_eligible(*d, False) else \
-            _splitk_plan(M, d.K // 64, stages)
-        if zn == 0 and stages >= 16 and not ext.conv8_eligible(*d, False):
-            # small-M long-reduction (r4-class 1x1): the 8-wave grid
-            # underfills without a K split — slice it so the 8-wave
-            # split-K launcher engages
-            mt8 = (M + 255) // 256
-            bn8 = 128 if d.K % 128 == 0 else 64
-            tiles8 = mt8 * (d.K // bn8)
-            if tiles8 and tiles8 < 160:
-                zn = min(max(2, -(-160 // tiles8)), 8, stages // 8)
-                zn = 0 if zn < 2 else zn
+        zn = 0
+        if not ext.conv8_eligible(*d, False):
+            zn = _splitk_plan(M, d.K // 64, stages) or \
+                _underfill_zn(M, d.K, stages)
         if zn:
             spz = (stages + zn - 1) // zn
             zeff = (stages + spz - 1) // spz
@@ -285,16 +293,11 @@ def conv_dgrad(dout: torch.Tensor, w_rsck: torch.Tensor, dx: torch.Tensor,
     M = d.N * d.H * d.W
     rsk = d.R * d.S * d.K
     stages = (rsk + 63) // 64
-    zn = 0 if ext.conv8_eligible(*d, True) else \
-        _splitk_plan(M, d.C // 64, stages)
-    if zn == 0 and stages >= 16 and d.stride == 1 \
-            and not ext.conv8_eligible(*d, True):
-        mt8 = (M + 255) // 256
-        bn8 = 128 if d.C % 128 == 0 else 64
-        tiles8 = mt8 * (d.C // bn8)
-        if tiles8 and tiles8 < 160:
-            zn = min(max(2, -(-160 // tiles8)), 8, stages // 8)
-            zn = 0 if zn < 2 else zn
+    zn = 0
+    if not ext.conv8_eligible(*d, True):
+        zn = _splitk_plan(M, d.C // 64, stages)
+        if zn == 0 and d.stride == 1:
+            zn = _underfill_zn(M, d.C, stages)
     if zn:
         spz = (stages + zn - 1) // zn
         zeff = (stages + spz - 1) // spz

@@ -32,7 +32,9 @@ def needs_build() -> bool:
     out = so_path()
     if not out.exists():
         return True
-    newest = max(p.stat().st_mtime for p in sources() + [CSRC / "common.h"])
+    # every header counts: the 8-wave kernel core lives in conv8.h
+    newest = max(p.stat().st_mtime
+                 for p in sources() + sorted(CSRC.glob("*.h")))
     return out.stat().st_mtime < newest
 
 

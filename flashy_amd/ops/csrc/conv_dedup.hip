@@ -15,16 +15,13 @@
 //   (hv rows outside the image and the side columns load hardware zeros
 //    via the buffer-bounds OOB sentinel, so tap reads need no branches)
 //
-// Same conventions as conv_fwd8.hip: 512 threads (2M x 4N waves), BN in
-// {64,128} over K, BK=64, source-side XOR swizzle + matching read XOR,
-// swapped MFMA operands -> packed 8 B stores, fused BN-stats epilogue.
-// The dgrad of these layers is dispatched through the same kernel with
-// remapped dims (A slab = dy, B = the RSCK-transposed weight, taps
-// reflected — see launch_conv_dedup_dgrad).
+// Same conventions as the rest of the 8-wave family: 512 threads
+// (2M x 4N waves), BN in {64,128} over K, BK=64, source-side XOR swizzle +
+// matching read XOR, swapped MFMA operands -> packed 8 B stores, fused
+// BN-stats epilogue.  Forward only: the dgrad of these layers runs on
+// k_conv_dgrad8.
 
-#include "conv_common.h"
-
-#define OOB_SENTINEL 0xF0000000u
+#include "conv8.h"
 
 template <int BN, bool RELU>
 __global__ void __launch_bounds__(512, 2)
@@ -73,7 +70,7 @@ k_conv_dedup(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
         const int kc_s = kc_d ^ (pix & 7);      // source-side swizzle
         const int hv = row_lo + pix / Wp;
         const int wi = pix % Wp - d.pad;
-        unsigned voff = OOB_SENTINEL;
+        unsigned voff = kOobSentinel;
         if (hv >= 0 && hv < d.H && wi >= 0 && wi < d.W)
             voff = (unsigned)((((n_img * d.H + hv) * d.W + wi) *
                                (int64_t)d.C + kc_s * 8) * 2);
@@ -261,16 +258,12 @@ k_conv_dedup(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
 // bn, tiles-per-image, slab rows and the dynamic-LDS element count.
 extern "C" int conv_dedup_plan(ConvDims d, int* bn_out, int* tpi_out,
                                int* rows_out, int* elems_out) {
-    static int disabled = [] {
-        const char* e = getenv("FLASHY_NO_FWD8");
-        return e && e[0] == '1';
-    }();
-    if (disabled) return 0;
+    if (conv8_disabled()) return 0;
     if (d.stride != 1 || d.Ho != d.H || d.Wo != d.W) return 0;
     if (d.R != 2 * d.pad + 1 || d.S != 2 * d.pad + 1 || d.R < 2) return 0;
     if ((d.C != 64 && d.C != 128) || d.K % 64) return 0;
     const int64_t x_elems = (int64_t)d.N * d.H * d.W * d.C;
-    if (x_elems * 2 >= (int64_t)OOB_SENTINEL) return 0;
+    if (x_elems * 2 >= (int64_t)kOobSentinel) return 0;
     const int64_t hw = (int64_t)d.Ho * d.Wo;
     const int tpi = (int)((hw + 255) / 256);
     // worst-case spanned output rows of a 256-pixel tile + halo
@@ -296,39 +289,22 @@ extern "C" void launch_conv_dedup(const void* x, const void* w, void* y,
     dim3 grid((unsigned)((int64_t)d.N * tpi), (unsigned)(d.K / bn));
     const unsigned xb = (unsigned)((int64_t)d.N * d.H * d.W * d.C * 2);
     const size_t shmem = (size_t)lds_elems * 2;
-    static bool attr_set = [] {
+    // first call: lift the dynamic-LDS cap of all four instantiations
+    static const bool attr_set = [] {
+        const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
         const int cap = 160 * 1024;
-        (void)hipFuncSetAttribute(
-            (const void*)&k_conv_dedup<128, true>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-        (void)hipFuncSetAttribute(
-            (const void*)&k_conv_dedup<128, false>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-        (void)hipFuncSetAttribute(
-            (const void*)&k_conv_dedup<64, true>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-        (void)hipFuncSetAttribute(
-            (const void*)&k_conv_dedup<64, false>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+        (void)hipFuncSetAttribute((const void*)&k_conv_dedup<128, true>, attr, cap);
+        (void)hipFuncSetAttribute((const void*)&k_conv_dedup<128, false>, attr, cap);
+        (void)hipFuncSetAttribute((const void*)&k_conv_dedup<64, true>, attr, cap);
+        (void)hipFuncSetAttribute((const void*)&k_conv_dedup<64, false>, attr, cap);
         return true;
     }();
     (void)attr_set;
-    auto xx = (const uint16_t*)x;
-    auto ww = (const uint16_t*)w;
-    auto yy = (uint16_t*)y;
-    if (bn == 128) {
-        if (relu)
-            k_conv_dedup<128, true><<<grid, 512, shmem, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb, tpi, rows, lds_elems);
-        else
-            k_conv_dedup<128, false><<<grid, 512, shmem, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb, tpi, rows, lds_elems);
-    } else {
-        if (relu)
-            k_conv_dedup<64, true><<<grid, 512, shmem, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb, tpi, rows, lds_elems);
-        else
-            k_conv_dedup<64, false><<<grid, 512, shmem, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb, tpi, rows, lds_elems);
-    }
+    dispatch8(bn, relu, [&](auto BN, auto RELU) {
+        k_conv_dedup<decltype(BN)::value, decltype(RELU)::value>
+            <<<grid, 512, shmem, stream>>>((const uint16_t*)x,
+                                           (const uint16_t*)w, (uint16_t*)y,
+                                           (float*)bn_ws, d, xb, tpi, rows,
+                                           lds_elems);
+    });
 }

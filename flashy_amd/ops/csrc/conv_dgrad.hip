@@ -13,7 +13,7 @@
 // an incremental (r,s,k) tap walk; B fragments load at use.
 // Requires: K % 64 == 0, C % 64 == 0.
 
-#include "conv_common.h"
+#include "conv8.h"
 
 template <int BM, bool SPLITK, bool S1, int SUBS = 2, int BN = CONV_BN>
 __global__ void __launch_bounds__(CONV_THREADS)
@@ -207,20 +207,6 @@ k_conv_dgrad(const uint16_t* __restrict__ dout, const uint16_t* __restrict__ w_r
 extern "C" int launch_conv_dgrad_s2(const void* dout, const void* w_rsck,
                                     void* dx, ConvDims d, hipStream_t stream);
 
-extern "C" int conv_dgrad8_plan(ConvDims d, int* bn_out);
-extern "C" void launch_conv_dgrad8(const void* dout, const void* w_rsck,
-                                   void* dx, ConvDims d, int bn, int mtiles,
-                                   hipStream_t stream);
-extern "C" int conv_dgrad8_s2_plan(ConvDims d, int* bn_out);
-extern "C" void launch_conv_dgrad8_s2(const void* dout, const void* w_rsck,
-                                      void* dx, ConvDims d, int bn,
-                                      int mtiles, hipStream_t stream);
-extern "C" int conv1x1_mloop_plan(ConvDims d, int* bn_out, int* gridx_out);
-extern "C" void launch_conv1x1_mloop(const void* x, const void* w, void* y,
-                                     ConvDims d, int relu, void* bn_ws,
-                                     int bn, int gridx, int mtiles,
-                                     hipStream_t stream);
-
 extern "C" void launch_conv_dgrad(const void* dout, const void* w_rsck,
                                   void* dx, ConvDims d, hipStream_t stream) {
     const int64_t M = (int64_t)d.N * d.H * d.W;
@@ -291,12 +277,6 @@ extern "C" void launch_conv_dgrad(const void* dout, const void* w_rsck,
     }
 }
 
-extern "C" void launch_conv_dgrad8_splitk(const void* dout,
-                                          const void* w_rsck, void* ws,
-                                          ConvDims d, int bn, int mtiles,
-                                          int spz, int zeff,
-                                          hipStream_t stream);
-
 extern "C" void launch_conv_dgrad_splitk(const void* dout, const void* w_rsck,
                                          void* ws, ConvDims d, int spz,
                                          hipStream_t stream) {
@@ -306,7 +286,7 @@ extern "C" void launch_conv_dgrad_splitk(const void* dout, const void* w_rsck,
     const int zeff = (all_stages + spz - 1) / spz;
     // 8-wave split-K for the small-M long-reduction layers (r4-class)
     if (d.C % 64 == 0 && d.K % 64 == 0 && rsk % 64 == 0 &&
-        (int64_t)d.N * d.Ho * d.Wo * d.K * 2 < (int64_t)0xF0000000u) {
+        (int64_t)d.N * d.Ho * d.Wo * d.K * 2 < (int64_t)kOobSentinel) {
         const int mtiles = (int)((M + 255) / 256);
         const int bn8 = d.C % 128 == 0 ? 128 : 64;
         if ((int64_t)mtiles * (d.C / bn8) * zeff >= 120) {

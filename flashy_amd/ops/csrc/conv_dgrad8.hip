@@ -10,12 +10,11 @@
 //   B[(r,s,k)][c] = w_rsck[r][s][c][k]  (8 consecutive k = 16 B).
 //
 // 512 threads (2M x 4N waves), BM=256 x BN in {64,128} over C, BK=64,
-// 3 LDS buffers, one raw barrier + counted vmcnt per stage, XOR-swizzled
-// images, setprio around MFMA.  Requires K % 64 == 0, C % 64 == 0.
+// 4 (BN=64) or 3 (BN=128) LDS buffers, one raw barrier + counted vmcnt per
+// stage, XOR-swizzled images, setprio around MFMA.  Requires K % 64 == 0,
+// C % 64 == 0.  Plans and launch dispatch are shared through conv8.h.
 
-#include "conv_common.h"
-
-#define OOB_SENTINEL 0xF0000000u
+#include "conv8.h"
 
 // SCAT2: 1x1 stride-2 dgrad as a quarter-size GEMM — dx is nonzero only at
 // even (hi, wi), so A rows are the OUTPUT pixels read linearly from dy and
@@ -105,7 +104,7 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
         uint16_t* base = lds + buf * BUF_ELEMS;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            unsigned voff = OOB_SENTINEL;
+            unsigned voff = kOobSentinel;
             if (SCAT2) {
                 if (a_n[g] >= 0)
                     voff = (unsigned)((a_n[g] * d.K + a_k[g]) * 2);
@@ -271,27 +270,14 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
     }
 }
 
-#include <cstdlib>
 extern "C" int conv_dgrad8_plan(ConvDims d, int* bn_out) {
-    static int disabled = [] {
-        const char* e = getenv("FLASHY_NO_FWD8");
-        return e && e[0] == '1';
-    }();
-    if (disabled) return 0;
+    if (conv8_disabled()) return 0;
     const int64_t M = (int64_t)d.N * d.H * d.W;
     if (d.C % 64 || d.K % 64) return 0;
     const int64_t dout_elems = (int64_t)d.N * d.Ho * d.Wo * d.K;
-    if (dout_elems * 2 >= (int64_t)OOB_SENTINEL) return 0;
+    if (dout_elems * 2 >= (int64_t)kOobSentinel) return 0;
     const int mtiles = (int)((M + 255) / 256);
-    if (d.C % 128 == 0 && (int64_t)mtiles * (d.C / 128) >= 160) {
-        *bn_out = 128;
-        return mtiles;
-    }
-    if ((int64_t)mtiles * (d.C / 64) >= 160) {
-        *bn_out = 64;
-        return mtiles;
-    }
-    return 0;
+    return pick_bn8(mtiles, d.C, 160, bn_out) ? mtiles : 0;
 }
 
 // 1x1 stride-2 plan: quarter-size GEMM over the output grid (SCAT2)
@@ -300,54 +286,39 @@ extern "C" int conv_dgrad8_s2_plan(ConvDims d, int* bn_out) {
     if (d.C % 64 || d.K % 64) return 0;
     const int64_t Mq = (int64_t)d.N * d.Ho * d.Wo;
     const int64_t dout_elems = Mq * d.K;
-    if (dout_elems * 2 >= (int64_t)OOB_SENTINEL) return 0;
+    if (dout_elems * 2 >= (int64_t)kOobSentinel) return 0;
     if (d.W % 2 || d.H % 2) return 0;   // sibling zero-stores assume even
     const int mtiles = (int)((Mq + 255) / 256);
-    if (d.C % 128 == 0 && (int64_t)mtiles * (d.C / 128) >= 104) {
-        *bn_out = 128;
-        return mtiles;
-    }
-    if ((int64_t)mtiles * (d.C / 64) >= 104) {
-        *bn_out = 64;
-        return mtiles;
-    }
-    return 0;
+    return pick_bn8(mtiles, d.C, 104, bn_out) ? mtiles : 0;
+}
+
+// The three launchers differ only in SCAT2 / SPLITK; S1 follows the stride
+// (SCAT2 reads dy linearly and ignores it).
+template <bool SCAT2_LAUNCH, bool SPLITK>
+static void launch_dgrad8(const void* dout, const void* w_rsck, void* out,
+                          ConvDims d, int bn, int mtiles, int spz, int zeff,
+                          hipStream_t stream) {
+    dim3 grid((unsigned)mtiles, (unsigned)(d.C / bn), (unsigned)zeff);
+    const unsigned db = (unsigned)((int64_t)d.N * d.Ho * d.Wo * d.K * 2);
+    dispatch8(bn, d.stride == 1, [&](auto BN, auto S1) {
+        constexpr bool s1 = !SCAT2_LAUNCH && decltype(S1)::value;
+        k_conv_dgrad8<decltype(BN)::value, s1, SCAT2_LAUNCH, SPLITK>
+            <<<grid, 512, 0, stream>>>((const uint16_t*)dout,
+                                       (const uint16_t*)w_rsck,
+                                       (uint16_t*)out, d, db, spz);
+    });
 }
 
 extern "C" void launch_conv_dgrad8_s2(const void* dout, const void* w_rsck,
                                       void* dx, ConvDims d, int bn,
                                       int mtiles, hipStream_t stream) {
-    dim3 grid((unsigned)mtiles, (unsigned)(d.C / bn));
-    const unsigned db =
-        (unsigned)((int64_t)d.N * d.Ho * d.Wo * d.K * 2);
-    auto dd = (const uint16_t*)dout;
-    auto ww = (const uint16_t*)w_rsck;
-    auto xx = (uint16_t*)dx;
-    if (bn == 128)
-        k_conv_dgrad8<128, false, true><<<grid, 512, 0, stream>>>(dd, ww, xx, d, db);
-    else
-        k_conv_dgrad8<64, false, true><<<grid, 512, 0, stream>>>(dd, ww, xx, d, db);
+    launch_dgrad8<true, false>(dout, w_rsck, dx, d, bn, mtiles, 0, 1, stream);
 }
 
 extern "C" void launch_conv_dgrad8(const void* dout, const void* w_rsck,
                                    void* dx, ConvDims d, int bn, int mtiles,
                                    hipStream_t stream) {
-    dim3 grid((unsigned)mtiles, (unsigned)(d.C / bn));
-    const unsigned db = (unsigned)((int64_t)d.N * d.Ho * d.Wo * d.K * 2);
-    auto dd = (const uint16_t*)dout;
-    auto ww = (const uint16_t*)w_rsck;
-    auto xx = (uint16_t*)dx;
-    if (bn == 128) {
-        if (d.stride == 1)
-            k_conv_dgrad8<128, true><<<grid, 512, 0, stream>>>(dd, ww, xx, d, db);
-        else
-            k_conv_dgrad8<128, false><<<grid, 512, 0, stream>>>(dd, ww, xx, d, db);
-    } else {
-        if (d.stride == 1)
-            k_conv_dgrad8<64, true><<<grid, 512, 0, stream>>>(dd, ww, xx, d, db);
-        else
-            k_conv_dgrad8<64, false><<<grid, 512, 0, stream>>>(dd, ww, xx, d, db);
-    }
+    launch_dgrad8<false, false>(dout, w_rsck, dx, d, bn, mtiles, 0, 1, stream);
 }
 
 extern "C" void launch_conv_dgrad8_splitk(const void* dout,
@@ -355,23 +326,6 @@ extern "C" void launch_conv_dgrad8_splitk(const void* dout,
                                           ConvDims d, int bn, int mtiles,
                                           int spz, int zeff,
                                           hipStream_t stream) {
-    dim3 grid((unsigned)mtiles, (unsigned)(d.C / bn), (unsigned)zeff);
-    const unsigned db = (unsigned)((int64_t)d.N * d.Ho * d.Wo * d.K * 2);
-    auto dd = (const uint16_t*)dout;
-    auto ww = (const uint16_t*)w_rsck;
-    if (bn == 128) {
-        if (d.stride == 1)
-            k_conv_dgrad8<128, true, false, true><<<grid, 512, 0, stream>>>(
-                dd, ww, (uint16_t*)ws, d, db, spz);
-        else
-            k_conv_dgrad8<128, false, false, true><<<grid, 512, 0, stream>>>(
-                dd, ww, (uint16_t*)ws, d, db, spz);
-    } else {
-        if (d.stride == 1)
-            k_conv_dgrad8<64, true, false, true><<<grid, 512, 0, stream>>>(
-                dd, ww, (uint16_t*)ws, d, db, spz);
-        else
-            k_conv_dgrad8<64, false, false, true><<<grid, 512, 0, stream>>>(
-                dd, ww, (uint16_t*)ws, d, db, spz);
-    }
+    launch_dgrad8<false, true>(dout, w_rsck, ws, d, bn, mtiles, spz, zeff,
+                               stream);
 }

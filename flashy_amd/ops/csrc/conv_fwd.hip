@@ -22,7 +22,7 @@
 // Requires: C % 8 == 0, K % 64 == 0, rsc % 32 == 0 (ResNet bodies; the
 // C=3 stem has its own direct kernels below).
 
-#include "conv_common.h"
+#include "conv8.h"
 
 template <int BM, bool RELU, bool SPLITK, int SUBS = 2, int BN = CONV_BN>
 __global__ void __launch_bounds__(CONV_THREADS)
@@ -379,69 +379,64 @@ static int conv_subs() {   // A/B switch: FLASHY_CONV_SUBS=1 -> 32-deep stages
     return v;
 }
 
-// 8-wave 256-row kernel (conv_fwd8.hip) — used for the large-M layers.
-extern "C" int conv_fwd8_plan(ConvDims d, int* bn_out);
-extern "C" void launch_conv_fwd8(const void* x, const void* w, void* y,
-                                 ConvDims d, int relu, void* bn_ws, int bn,
-                                 int mtiles, hipStream_t stream);
-extern "C" int conv1x1_mloop_plan(ConvDims d, int* bn_out, int* gridx_out);
-extern "C" int conv_dedup_plan(ConvDims d, int* bn_out, int* tpi_out,
-                               int* rows_out, int* elems_out);
-extern "C" void launch_conv_dedup(const void* x, const void* w, void* y,
-                                  ConvDims d, int relu, void* bn_ws, int bn,
-                                  int tpi, int rows, int lds_elems,
-                                  hipStream_t stream);
-extern "C" void launch_conv1x1_mloop(const void* x, const void* w, void* y,
-                                     ConvDims d, int relu, void* bn_ws,
-                                     int bn, int gridx, int mtiles,
-                                     hipStream_t stream);
+// The ONE fwd dispatch chain: dedup -> mloop -> fwd8 -> 4-wave pick_tile.
+// Both the launcher and conv_fwd_msplit (BN-partials sizing) read it, so
+// they cannot disagree.
+enum FwdPath { FWD_DEDUP, FWD_MLOOP, FWD_8WAVE, FWD_TILE4 };
+struct ConvFwdPlan {
+    FwdPath path;
+    int bn, gridx;
+    int msplit;                   // slices of the fused BN-stats partials
+    int tpi, rows, lds_elems;     // dedup
+    int mtiles;                   // mloop (gridx blocks walk mtiles tiles)
+    int bm;                       // 4-wave tile
+};
 
-// grid.x the fwd launcher will use for these dims (= the msplit of the
-// fused BN-stats partials); Python sizes the partials buffer with this.
-extern "C" int conv_fwd_msplit(ConvDims d) {
-    int bn8, gx;
-    {
-        int tpi, rows, elems;
-        const int gd = conv_dedup_plan(d, &bn8, &tpi, &rows, &elems);
-        if (gd) return gd;
+static ConvFwdPlan conv_fwd_plan(ConvDims d) {
+    ConvFwdPlan p = {};
+    if ((p.gridx = conv_dedup_plan(d, &p.bn, &p.tpi, &p.rows, &p.lds_elems))) {
+        p.path = FWD_DEDUP;
+        p.msplit = p.gridx;
+    } else if ((p.mtiles = conv1x1_mloop_plan(d, &p.bn, &p.gridx))) {
+        p.path = FWD_MLOOP;
+        p.msplit = 2 * p.mtiles;   // per-(tile, wave_m) slices
+    } else if ((p.gridx = conv_fwd8_plan(d, &p.bn))) {
+        p.path = FWD_8WAVE;
+        p.msplit = p.gridx;
+    } else {
+        const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
+        p.path = FWD_TILE4;
+        pick_tile(M, d.K, &p.bm, &p.bn);
+        p.msplit = p.gridx = (int)((M + p.bm - 1) / p.bm);
     }
-    const int mtl = conv1x1_mloop_plan(d, &bn8, &gx);
-    if (mtl) return 2 * mtl;   // per-(tile, wave_m) slices
-    const int mt8 = conv_fwd8_plan(d, &bn8);
-    if (mt8) return mt8;
-    const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
-    int bm, bn;
-    pick_tile(M, d.K, &bm, &bn);
-    return (int)((M + bm - 1) / bm);
+    return p;
 }
+
+// msplit of the fused BN-stats partials the fwd launcher will write for
+// these dims; Python sizes the partials buffer with this.
+extern "C" int conv_fwd_msplit(ConvDims d) { return conv_fwd_plan(d).msplit; }
 
 extern "C" void launch_conv_fwd(const void* x, const void* w, void* y,
                                 ConvDims d, int relu, void* bn_ws,
                                 hipStream_t stream) {
-    int bn8, gx;
-    {
-        int tpi, rows, elems;
-        const int gd = conv_dedup_plan(d, &bn8, &tpi, &rows, &elems);
-        if (gd) {
-            launch_conv_dedup(x, w, y, d, relu, bn_ws, bn8, tpi, rows,
-                              elems, stream);
-            return;
-        }
-    }
-    const int mtl = conv1x1_mloop_plan(d, &bn8, &gx);
-    if (mtl) {
-        launch_conv1x1_mloop(x, w, y, d, relu, bn_ws, bn8, gx, mtl, stream);
+    const ConvFwdPlan p = conv_fwd_plan(d);
+    switch (p.path) {
+    case FWD_DEDUP:
+        launch_conv_dedup(x, w, y, d, relu, bn_ws, p.bn, p.tpi, p.rows,
+                          p.lds_elems, stream);
         return;
-    }
-    const int mt8 = conv_fwd8_plan(d, &bn8);
-    if (mt8) {
-        launch_conv_fwd8(x, w, y, d, relu, bn_ws, bn8, mt8, stream);
+    case FWD_MLOOP:
+        launch_conv1x1_mloop(x, w, y, d, relu, bn_ws, p.bn, p.gridx,
+                             p.mtiles, stream);
         return;
+    case FWD_8WAVE:
+        launch_conv_fwd8(x, w, y, d, relu, bn_ws, p.bn, p.gridx, stream);
+        return;
+    case FWD_TILE4:
+        break;
     }
-    const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
-    int bm, bn;
-    pick_tile(M, d.K, &bm, &bn);
-    dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)(d.K / bn));
+    const int bm = p.bm, bn = p.bn;
+    dim3 grid((unsigned)p.gridx, (unsigned)(d.K / bn));
     if (bn == 128) {
         auto xx = (const uint16_t*)x;
         auto ww = (const uint16_t*)w;
@@ -480,11 +475,6 @@ extern "C" void launch_conv_fwd(const void* x, const void* w, void* y,
 
 // split-K path: BM=64 tiles, grid.z over stage ranges, fp32 workspace
 // [zn][M][K], then k_splitk_combine.
-extern "C" void launch_conv_fwd8_splitk(const void* x, const void* w,
-                                        void* ws, ConvDims d, int bn,
-                                        int mtiles, int spz, int zeff,
-                                        hipStream_t stream);
-
 extern "C" void launch_conv_fwd_splitk(const void* x, const void* w, void* ws,
                                        ConvDims d, int spz, hipStream_t stream) {
     const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
@@ -494,7 +484,7 @@ extern "C" void launch_conv_fwd_splitk(const void* x, const void* w, void* ws,
     // 8-wave split-K for the small-M long-reduction layers (r4-class):
     // same Python-decided spz/zeff and ws layout, deeper pipeline
     if (d.C % 64 == 0 && d.K % 64 == 0 && rsc % 64 == 0 &&
-        (int64_t)d.N * d.H * d.W * d.C * 2 < (int64_t)0xF0000000u) {
+        (int64_t)d.N * d.H * d.W * d.C * 2 < (int64_t)kOobSentinel) {
         const int mtiles = (int)((M + 255) / 256);
         const int bn8 = d.K % 128 == 0 ? 128 : 64;
         if ((int64_t)mtiles * (d.K / bn8) * zeff >= 120) {

@@ -9,25 +9,19 @@
 //     descriptor's bounds check — out-of-range taps load hardware zeros
 //     (voffset sentinel far past num_bytes), so the inner loop has ZERO
 //     branches;
-//   * 3 LDS buffers, ONE raw `s_barrier` per 64-deep stage, counted
-//     `s_waitcnt vmcnt(G)` so the next stage's DMA stays in flight across
-//     the barrier (never vmcnt(0) in the main loop);
-//   * LDS images [rows][64] bf16 (128 B rows) XOR-swizzled by
-//     `byte ^= (row&7)<<4` — applied on the glds SOURCE chunk index and the
-//     `ds_read_b128` byte address (guide §5.4 rule 21), so the 16-lane b128
-//     groups stay <=2-way bank-conflicted;
-//   * `s_setprio(1)` around each MFMA cluster (T5: pays on phase-split
-//     8-wave schedules).
+//   * 4 (BN=64) or 3 (BN=128) LDS buffers, ONE raw `s_barrier` per 64-deep
+//     stage, counted `s_waitcnt vmcnt` so the next one or two stages' DMA
+//     stays in flight across the barrier (never vmcnt(0) in the main loop);
+//   * swizzled LDS images, swapped-operand MFMA clusters under
+//     `s_setprio`, packed 8 B stores.
+//
+// Plans, launch dispatch and the OOB sentinel are shared through conv8.h.
 //
 // Used for the large-M ResNet-50/224-class layers (C%64==0, K%64==0,
 // tensor < 2 GB); small-M / long-K shapes stay on the 4-wave split-K
 // kernel in conv_fwd.hip.  GEMM view and layouts as in conv_fwd.hip.
 
-#include "conv_common.h"
-
-// out-of-range sentinel: voffset far past any real tensor (tensors routed
-// here are < 2^31 - 2^28 bytes); the buffer bounds check returns zeros.
-#define OOB_SENTINEL 0xF0000000u
+#include "conv8.h"
 
 template <int BN, bool RELU, bool SPLITK = false>
 __global__ void __launch_bounds__(512, 2)
@@ -107,7 +101,7 @@ k_conv_fwd8(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
         uint16_t* base = lds + buf * BUF_ELEMS;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            unsigned voff = OOB_SENTINEL;
+            unsigned voff = kOobSentinel;
             if (a_n[g] >= 0 && a_r[g] < d.R) {
                 const int hi = a_hi0[g] + a_r[g];
                 const int wi = a_wi0[g] + a_s[g];
@@ -370,7 +364,7 @@ k_conv1x1_mloop(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
         for (int g = 0; g < 4; ++g) {
             const int64_t m = tile * 256 + a_row[g];
             const unsigned voff = m < M
-                ? (unsigned)((m * BK + a_koff[g]) * 2) : OOB_SENTINEL;
+                ? (unsigned)((m * BK + a_koff[g]) * 2) : kOobSentinel;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(
                 xrsrc,
                 (__attribute__((address_space(3))) void*)
@@ -496,16 +490,12 @@ k_conv1x1_mloop(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
 }
 
 extern "C" int conv1x1_mloop_plan(ConvDims d, int* bn_out, int* gridx_out) {
-    static int disabled = [] {
-        const char* e = getenv("FLASHY_NO_FWD8");
-        return e && e[0] == '1';
-    }();
-    if (disabled) return 0;
+    if (conv8_disabled()) return 0;
     if (d.R != 1 || d.S != 1 || d.stride != 1 || d.pad != 0) return 0;
     if (d.C != 64 || d.K % 64) return 0;
     const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
     const int64_t x_elems = (int64_t)d.N * d.H * d.W * d.C;
-    if (x_elems * 2 >= (int64_t)OOB_SENTINEL) return 0;
+    if (x_elems * 2 >= (int64_t)kOobSentinel) return 0;
     const int mtiles = (int)((M + 255) / 256);
     if (mtiles < 128) return 0;
     const int bn = d.K % 128 == 0 ? 128 : 64;
@@ -523,40 +513,12 @@ extern "C" void launch_conv1x1_mloop(const void* x, const void* w, void* y,
                                      hipStream_t stream) {
     dim3 grid((unsigned)gridx, (unsigned)(d.K / bn));
     const unsigned xb = (unsigned)((int64_t)d.N * d.H * d.W * d.C * 2);
-    auto xx = (const uint16_t*)x;
-    auto ww = (const uint16_t*)w;
-    auto yy = (uint16_t*)y;
-    if (bn == 128) {
-        if (relu)
-            k_conv1x1_mloop<128, true><<<grid, 512, 0, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb, mtiles);
-        else
-            k_conv1x1_mloop<128, false><<<grid, 512, 0, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb, mtiles);
-    } else {
-        if (relu)
-            k_conv1x1_mloop<64, true><<<grid, 512, 0, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb, mtiles);
-        else
-            k_conv1x1_mloop<64, false><<<grid, 512, 0, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb, mtiles);
-    }
-}
-
-extern "C" void launch_conv_fwd8_splitk(const void* x, const void* w,
-                                        void* ws, ConvDims d, int bn,
-                                        int mtiles, int spz, int zeff,
-                                        hipStream_t stream) {
-    dim3 grid((unsigned)mtiles, (unsigned)(d.K / bn), (unsigned)zeff);
-    const unsigned xb = (unsigned)((int64_t)d.N * d.H * d.W * d.C * 2);
-    auto xx = (const uint16_t*)x;
-    auto wv = (const uint16_t*)w;
-    if (bn == 128)
-        k_conv_fwd8<128, false, true><<<grid, 512, 0, stream>>>(
-            xx, wv, nullptr, (float*)ws, d, xb, spz);
-    else
-        k_conv_fwd8<64, false, true><<<grid, 512, 0, stream>>>(
-            xx, wv, nullptr, (float*)ws, d, xb, spz);
+    dispatch8(bn, relu, [&](auto BN, auto RELU) {
+        k_conv1x1_mloop<decltype(BN)::value, decltype(RELU)::value>
+            <<<grid, 512, 0, stream>>>((const uint16_t*)x, (const uint16_t*)w,
+                                       (uint16_t*)y, (float*)bn_ws, d, xb,
+                                       mtiles);
+    });
 }
 
 // --- stem padding helpers ---------------------------------------------------
@@ -638,32 +600,16 @@ extern "C" void launch_stem_unpad_dw(const void* dwp, void* dw, int K, int R,
         (const float*)dwp, (float*)dw, K, R, S);
 }
 
-// --- dispatch ---------------------------------------------------------------
-// Eligibility + grid for the 8-wave kernel; returns grid.x (m-tiles) or 0.
-// Decided purely from the dims so conv_fwd_msplit (BN-partials sizing) and
-// the launcher always agree.
-#include <cstdlib>
+// --- fwd8 plan + launchers ----------------------------------------------------
 extern "C" int conv_fwd8_plan(ConvDims d, int* bn_out) {
-    static int disabled = [] {
-        const char* e = getenv("FLASHY_NO_FWD8");
-        return e && e[0] == '1';
-    }();
-    if (disabled) return 0;
+    if (conv8_disabled()) return 0;
     const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
     const int rsc = d.R * d.S * d.C;
     if (d.C % 64 || d.K % 64 || rsc % 64) return 0;
     const int64_t x_elems = (int64_t)d.N * d.H * d.W * d.C;
-    if (x_elems * 2 >= (int64_t)OOB_SENTINEL) return 0;   // 32-bit voffset
+    if (x_elems * 2 >= (int64_t)kOobSentinel) return 0;   // 32-bit voffset
     const int mtiles = (int)((M + 255) / 256);
-    if (d.K % 128 == 0 && (int64_t)mtiles * (d.K / 128) >= 160) {
-        *bn_out = 128;
-        return mtiles;
-    }
-    if ((int64_t)mtiles * (d.K / 64) >= 160) {
-        *bn_out = 64;
-        return mtiles;
-    }
-    return 0;
+    return pick_bn8(mtiles, d.K, 160, bn_out) ? mtiles : 0;
 }
 
 extern "C" void launch_conv_fwd8(const void* x, const void* w, void* y,
@@ -671,22 +617,25 @@ extern "C" void launch_conv_fwd8(const void* x, const void* w, void* y,
                                  int mtiles, hipStream_t stream) {
     dim3 grid((unsigned)mtiles, (unsigned)(d.K / bn));
     const unsigned xb = (unsigned)((int64_t)d.N * d.H * d.W * d.C * 2);
+    dispatch8(bn, relu, [&](auto BN, auto RELU) {
+        k_conv_fwd8<decltype(BN)::value, decltype(RELU)::value>
+            <<<grid, 512, 0, stream>>>((const uint16_t*)x, (const uint16_t*)w,
+                                       (uint16_t*)y, (float*)bn_ws, d, xb);
+    });
+}
+
+extern "C" void launch_conv_fwd8_splitk(const void* x, const void* w,
+                                        void* ws, ConvDims d, int bn,
+                                        int mtiles, int spz, int zeff,
+                                        hipStream_t stream) {
+    dim3 grid((unsigned)mtiles, (unsigned)(d.K / bn), (unsigned)zeff);
+    const unsigned xb = (unsigned)((int64_t)d.N * d.H * d.W * d.C * 2);
     auto xx = (const uint16_t*)x;
     auto ww = (const uint16_t*)w;
-    auto yy = (uint16_t*)y;
-    if (bn == 128) {
-        if (relu)
-            k_conv_fwd8<128, true><<<grid, 512, 0, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb);
-        else
-            k_conv_fwd8<128, false><<<grid, 512, 0, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb);
-    } else {
-        if (relu)
-            k_conv_fwd8<64, true><<<grid, 512, 0, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb);
-        else
-            k_conv_fwd8<64, false><<<grid, 512, 0, stream>>>(
-                xx, ww, yy, (float*)bn_ws, d, xb);
-    }
+    if (bn == 128)
+        k_conv_fwd8<128, false, true><<<grid, 512, 0, stream>>>(
+            xx, ww, nullptr, (float*)ws, d, xb, spz);
+    else
+        k_conv_fwd8<64, false, true><<<grid, 512, 0, stream>>>(
+            xx, ww, nullptr, (float*)ws, d, xb, spz);
 }

@@ -11,24 +11,14 @@
 #include <cstdint>
 #include <stdexcept>
 
-namespace py = pybind11;
+#include "conv8.h"   // ConvDims + the 8-wave plan/launch prototypes
 
-struct ConvDims {
-    int N, H, W, C;
-    int K, R, S;
-    int Ho, Wo;
-    int stride, pad;
-};
+namespace py = pybind11;
 
 extern "C" {
 void launch_conv_fwd(const void* x, const void* w, void* y, ConvDims d,
                      int relu, void* bn_ws, hipStream_t stream);
 int conv_fwd_msplit(ConvDims d);
-int conv_fwd8_plan(ConvDims d, int* bn_out);
-int conv_dgrad8_plan(ConvDims d, int* bn_out);
-void launch_conv_fwd8(const void* x, const void* w, void* y, ConvDims d,
-                      int relu, void* bn_ws, int bn, int mtiles,
-                      hipStream_t stream);
 void launch_stem_pad_x(const void* x, void* xp, int64_t N, int H, int W,
                        int Hp, int Wp, int pad, hipStream_t stream);
 void launch_stem_pad_w(const void* w, void* wp, int K, int R, int S,

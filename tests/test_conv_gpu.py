@@ -257,7 +257,10 @@ def test_conv_fused_bn_stats():
     """The conv epilogue's fused BN partials must reproduce the standalone
     bn_stats sums (finalize consumes either)."""
     from flashy_amd import ops
-    N, H, W, C, K = 64, 16, 16, 64, 128   # M large: non-split-K path
+    # single-pass path, but 64 to 128 tiles is under the 160-block floor of
+    # every 8-wave plan: this exercises the 4-wave tile's stats epilogue
+    # (the 8-wave epilogues are covered in test_conv8_gpu.py)
+    N, H, W, C, K = 64, 16, 16, 64, 128
     x, w = _mk(N, H, W, C, K, 3)
     d = ops.ConvDims.infer(x, w, 1, 1)
     y = x.new_empty((d.N, d.Ho, d.Wo, d.K))

@@ -29,6 +29,39 @@ def test_splitk_plan_regimes():
     assert ops._splitk_plan(64, 1, 200) <= 8
 
 
+def test_needs_build_sees_every_header(tmp_path, monkeypatch):
+    """An edit to ANY csrc header (the 8-wave kernel core lives in one) must
+    invalidate the built extension.  Paths are redirected to a scratch
+    directory; nothing is compiled."""
+    import os
+    from flashy_amd.ops import build
+    csrc = tmp_path / "csrc"
+    csrc.mkdir()
+    for name in ("a.hip", "ext.cpp", "common.h", "conv8.h"):
+        (csrc / name).write_text("// stub\n")
+        os.utime(csrc / name, (1000, 1000))
+    so = tmp_path / "_hip_ops.so"
+    so.write_bytes(b"")
+    os.utime(so, (2000, 2000))
+    monkeypatch.setattr(build, "CSRC", csrc)
+    monkeypatch.setattr(build, "so_path", lambda: so)
+    assert not build.needs_build()
+    for name in ("conv8.h", "common.h", "a.hip", "ext.cpp"):
+        os.utime(csrc / name, (3000, 3000))
+        assert build.needs_build(), name
+        os.utime(csrc / name, (1000, 1000))
+    assert not build.needs_build()
+    so.unlink()
+    assert build.needs_build()
+
+
+def test_underfill_zn():
+    # r4-class dgrad (64,7,7,512,192,3x3): 52 tiles, 27 stages -> 3 slices
+    assert ops._underfill_zn(3136, 512, 27) == 3
+    assert ops._underfill_zn(3136, 512, 15) == 0     # short reduction
+    assert ops._underfill_zn(64 * 56 * 56, 256, 64) == 0   # grid already full
+
+
 def test_bn_msplit_alignment():
     for M, C in [(65536, 64), (16384, 128), (1024, 512), (48, 64)]:
         ms = ops.bn_msplit(M, C)
