@@ -3,9 +3,11 @@
 //
 // GEMM view:  dW[K][rsc] += A'[K][M] * B'[M][rsc]
 //   A' = dout^T  (dout is [M][K] NHWC),  B' = implicit im2col of x,
-//   reduction over M = N*Ho*Wo, split across grid.z blocks, fp32
-//   atomicAdd into the flat fp32 gradient view (accumulate semantics match
-//   autograd, and zero_grad() memsets the flat buffer).
+//   reduction over M = N*Ho*Wo, split into m-ranges; the wave groups of a
+//   block sum their ranges in LDS, blocks sharing a tile add into the flat
+//   fp32 gradient view with fp32 atomicAdd, a tile's only block with a plain
+//   load-add-store (accumulate semantics match autograd, and zero_grad()
+//   memsets the flat buffer).
 //
 // Both operands arrive [m][channel]-contiguous.  They are staged into LDS
 // AS-LOADED ([m][channel] rows, one b128 store per thread per tensor per
@@ -25,25 +27,54 @@
 #include "conv_common.h"
 
 #define WG_P 72  // LDS row pitch in bf16 elements (144 B = 9 * 16 B)
+#define WG_STAGE (2 * 32 * WG_P)       // one operand's stage image: [sc 2][m 32][WG_P]
+#define WG_GROUP_ELEMS (4 * WG_STAGE)  // dout[2] + x[2] of one wave group (36,864 B)
+#define WG_GROUP_BYTES (WG_GROUP_ELEMS * 2)
+#define WG_TP 68  // fp32 pitch of the epilogue tile: the 16x16 accumulator's four
+                  // row groups land 272 dwords apart = banks 0/16/32/48
 
-__global__ void __launch_bounds__(CONV_THREADS, 4)  // cap at 128 VGPR
+// MG wave groups of 4 waves per block.  Group g reduces m-range
+// blockIdx.z*MG + g with its own pair of staging buffers, exactly the
+// 4-wave schedule described above; the epilogue then sums the MG 64x64
+// tiles in LDS (fixed group order) and adds whole 256-byte rows to dw, so a
+// call issues 1/MG of the atomic bytes, each wave-instruction in the
+// full-rate shape (global float atomics run at the memory side, ~1.3 TB/s
+// chip-wide).  `single` (grid.z == 1: one adder block per tile) replaces
+// the atomic by a plain load-add-store: race-free and bitwise reproducible.
+// MG = 1 with several adder blocks has nothing to sum and adds straight from
+// the accumulators.
+//
+// Barriers are block-wide, so every group runs the SAME stage count: that
+// of group 0.  Ranges are consecutive and only the last range of the call
+// is short, so group 0's range is the longest in the block; a group whose
+// range is shorter or empty (ms == me == M) stages zeros for the missing
+// rows (load_pair never reads at or past `me`).
+template <int MG>
+__global__ void __launch_bounds__(CONV_THREADS * MG, 4)  // cap at 128 VGPR
 k_conv_wgrad(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dout,
-             float* __restrict__ dw, ConvDims d, int m_per_split) {
+             float* __restrict__ dw, ConvDims d, int m_per_split, int single) {
     const int rsc = d.R * d.S * d.C;
     const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
-    const int tid = threadIdx.x;
+    const int grp = threadIdx.x / CONV_THREADS;   // wave group
+    const int tid = threadIdx.x % CONV_THREADS;   // thread within the group
     const int lane = tid & 63;
     const int wid = tid >> 6;
     const int wave_k = wid >> 1;   // K halves (32 rows each)
     const int wave_j = wid & 1;    // rsc halves
     const int k0 = blockIdx.x * 64;
     const int j0 = blockIdx.y * 64;
-    const int64_t ms = (int64_t)blockIdx.z * m_per_split;
+    const int64_t ms0 = (int64_t)blockIdx.z * MG * m_per_split;   // < M
+    const int64_t ms = min(ms0 + (int64_t)grp * m_per_split, M);
     const int64_t me = min(ms + (int64_t)m_per_split, M);
 
-    // [buffer][subchunk 2][m 32][WG_P], rows as loaded from global
-    __shared__ __attribute__((aligned(16))) uint16_t doutT[2][2 * 32 * WG_P];
-    __shared__ __attribute__((aligned(16))) uint16_t xT[2][2 * 32 * WG_P];
+    // per group: [dout buf 0][dout buf 1][x buf 0][x buf 1], each
+    // [subchunk 2][m 32][WG_P], rows as loaded from global
+    extern __shared__ __attribute__((aligned(16))) uint16_t wg_lds[];
+    uint16_t* const gbase = wg_lds + grp * WG_GROUP_ELEMS;
+    uint16_t* const doutT0 = gbase;
+    uint16_t* const doutT1 = gbase + WG_STAGE;
+    uint16_t* const xT0 = gbase + 2 * WG_STAGE;
+    uint16_t* const xT1 = gbase + 3 * WG_STAGE;
 
     floatx4 acc[2][2] = {};
 
@@ -80,8 +111,7 @@ k_conv_wgrad(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dout,
             xv[sc] = u;
         }
     };
-    auto stage_write = [&](uint16_t (&dT)[2 * 32 * WG_P],
-                           uint16_t (&xTb)[2 * 32 * WG_P],
+    auto stage_write = [&](uint16_t* dT, uint16_t* xTb,
                            const short8* dv, const short8* xv) {
 #pragma unroll
         for (int sc = 0; sc < 2; ++sc) {
@@ -98,17 +128,18 @@ k_conv_wgrad(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dout,
                         (lane >> 4) * 8 * WG_P;
     union U64x2 { struct { unsigned long long lo, hi; } q; short8 v; };
 
-    const int64_t n_stages = (me - ms + 2 * CONV_BK - 1) / (2 * CONV_BK);
+    // block-uniform: group 0's stage count (see the header comment)
+    const int64_t n_stages =
+        (min(ms0 + (int64_t)m_per_split, M) - ms0 + 2 * CONV_BK - 1) /
+        (2 * CONV_BK);
     short8 dv[2], xv[2];
     load_pair(ms, dv, xv);
-    stage_write(doutT[0], xT[0], dv, xv);
+    stage_write(doutT0, xT0, dv, xv);
     if (n_stages > 1) load_pair(ms + 2 * CONV_BK, dv, xv);
     __syncthreads();
 
-    auto step = [&](int64_t i, const uint16_t (&dT)[2 * 32 * WG_P],
-                    const uint16_t (&xTb)[2 * 32 * WG_P],
-                    uint16_t (&ndT)[2 * 32 * WG_P],
-                    uint16_t (&nxT)[2 * 32 * WG_P]) {
+    auto step = [&](int64_t i, const uint16_t* dT, const uint16_t* xTb,
+                    uint16_t* ndT, uint16_t* nxT) {
         if (i + 1 < n_stages) {
             stage_write(ndT, nxT, dv, xv);
             if (i + 2 < n_stages) load_pair(ms + (i + 2) * 2 * CONV_BK, dv, xv);
@@ -171,25 +202,60 @@ k_conv_wgrad(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dout,
         __syncthreads();
     };
     for (int64_t i = 0; i < n_stages;) {
-        step(i, doutT[0], xT[0], doutT[1], xT[1]);
+        step(i, doutT0, xT0, doutT1, xT1);
         if (++i >= n_stages) break;
-        step(i, doutT[1], xT[1], doutT[0], xT[0]);
+        step(i, doutT1, xT1, doutT0, xT0);
         ++i;
     }
 
     // ---- accumulate into fp32 dw (flat KRSC layout) ---------------------
-    const int out_k0 = k0 + wave_k * 32 + (lane >> 4) * 4;
-    const int out_j0 = j0 + wave_j * 32 + (lane & 15);
+    // The last stage's barrier is behind every LDS read, so each group's
+    // staging area is free: park the group's 64x64 fp32 tile there.
+    const int t_k = wave_k * 32 + (lane >> 4) * 4;
+    const int t_j = wave_j * 32 + (lane & 15);
+    if constexpr (MG == 1) {
+        // Nothing to sum on chip: add straight from the accumulators.  The
+        // row-shaped adds below are not faster by themselves (measured
+        // neutral on 3x3, 13.6 vs 10.4 us on the 128->256 1x1), and this
+        // keeps the ungrouped dispatch at its previous cost.  `single` is
+        // block-uniform, and no barrier follows.
+        if (!single) {
+#pragma unroll
+            for (int kf = 0; kf < 2; ++kf)
+#pragma unroll
+                for (int jf = 0; jf < 2; ++jf)
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr)
+                        atomicAdd(&dw[(int64_t)(k0 + t_k + kf * 16 + rr) * rsc +
+                                      j0 + t_j + jf * 16],
+                                  acc[kf][jf][rr]);
+            return;
+        }
+    }
+    float* const tile = reinterpret_cast<float*>(gbase);   // [64][WG_TP]
 #pragma unroll
     for (int kf = 0; kf < 2; ++kf)
 #pragma unroll
         for (int jf = 0; jf < 2; ++jf)
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int k = out_k0 + kf * 16 + rr;
-                const int j = out_j0 + jf * 16;
-                atomicAdd(&dw[(int64_t)k * rsc + j], acc[kf][jf][rr]);
-            }
+            for (int rr = 0; rr < 4; ++rr)
+                tile[(t_k + kf * 16 + rr) * WG_TP + t_j + jf * 16] =
+                    acc[kf][jf][rr];
+    __syncthreads();   // reached by all 4*MG waves: nothing above diverges
+    // wave w owns tile rows w, w + 4*MG, ...: one wave-instruction = 64
+    // consecutive j of one k = 256 contiguous bytes of dw
+    const float* const tiles = reinterpret_cast<const float*>(wg_lds);
+    for (int r = threadIdx.x >> 6; r < 64; r += 4 * MG) {
+        float v = tiles[r * WG_TP + lane];
+#pragma unroll
+        for (int g = 1; g < MG; ++g)
+            v += tiles[g * (WG_GROUP_BYTES / 4) + r * WG_TP + lane];
+        float* const p = &dw[(int64_t)(k0 + r) * rsc + j0 + lane];
+        if (single)
+            *p += v;
+        else
+            atomicAdd(p, v);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -207,7 +273,7 @@ k_conv_wgrad(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dout,
 
 __global__ void __launch_bounds__(512, 2)
 k_conv_wgrad8(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dout,
-              float* __restrict__ dw, ConvDims d, int m_per_split) {
+              float* __restrict__ dw, ConvDims d, int m_per_split, int single) {
     const int rsc = d.R * d.S * d.C;
     const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
     const int tid = threadIdx.x;
@@ -368,8 +434,77 @@ k_conv_wgrad8(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dout,
             for (int rr = 0; rr < 4; ++rr) {
                 const int k = out_k0 + kf * 16 + rr;
                 const int j = out_j0 + jf * 16;
-                atomicAdd(&dw[(int64_t)k * rsc + j], acc[kf][jf][rr]);
+                float* const p = &dw[(int64_t)k * rsc + j];
+                if (single)   // grid.z == 1: this block owns the tile
+                    *p += acc[kf][jf][rr];
+                else
+                    atomicAdd(p, acc[kf][jf][rr]);
             }
+}
+
+#include <cstdlib>
+// FLASHY_WGRAD_MG=1|2|4 pins the wave-group count of k_conv_wgrad (read on
+// every call: scripts/wgrad_sweep.py and the tests flip it in-process).
+static int wgrad_mg_forced() {
+    const char* e = getenv("FLASHY_WGRAD_MG");
+    if (e && (e[0] == '1' || e[0] == '2' || e[0] == '4') && !e[1])
+        return e[0] - '0';
+    return 0;
+}
+
+// Largest MG the measured sweep (profiles/r04a_wgrad_sweep.txt) supports.
+// A CU holds 16 waves of this kernel = 4/MG blocks, so 1024/MG blocks run at
+// once on the 256 CUs.  Grouping must not
+//   - add a round of blocks over MG = 1 (MG = 2 may overfill by 1/8: its
+//     half-CU blocks backfill, 576 blocks on 512 slots still won at
+//     256->256 3x3; 288 one-per-CU blocks of MG = 4 lost by 25%),
+//   - pad the ranges by more than 1/5 with empty groups, which run the full
+//     stage count on zeros (3 ranges as 2x2 lost at 256->512 stride 2),
+//   - leave CUs idle that MG = 1 would fill: 9/10 of them when the stage loop
+//     dominates (the 1x1 64->256 ResNet-50 shape lost 34% on 128 blocks), half
+//     when a range is at most two stages and the epilogue dominates (the
+//     CIFAR 1x1 downsamples),
+// and is not tried where a range is longer than 16 stages: the adds are then
+// under 1/16 of the block's traffic, and the ResNet-50/224 64->64 3x3 and
+// 64->256 1x1 shapes measured neutral to 4% slower grouped.
+static int wgrad_pick_mg(int tiles, int ranges, int m_per_split) {
+    if (m_per_split > 32 * CONV_BK) return 1;
+    const int64_t blocks1 = (int64_t)tiles * ranges;
+    const int64_t rounds1 = (blocks1 + 1023) / 1024;
+    const int64_t fill1 = blocks1 < 256 ? blocks1 : 256;
+    const bool short_range = m_per_split <= 4 * CONV_BK;
+    for (int mg = 4; mg > 1; mg >>= 1) {
+        if (mg > ranges) continue;
+        const int zn = (ranges + mg - 1) / mg;
+        const int64_t blocks = (int64_t)tiles * zn;
+        const int64_t slots = 1024 / mg;
+        const bool fits = blocks <= slots * rounds1 + (mg == 2 ? slots / 8 : 0);
+        const bool padded = (mg * zn - ranges) * 5 > ranges;
+        const bool filled = short_range ? blocks * 2 >= fill1
+                                        : blocks * 10 >= fill1 * 9;
+        if (fits && !padded && filled) return mg;
+    }
+    return 1;
+}
+
+template <int MG>
+static void launch_wgrad_mg(const void* x, const void* dout, void* dw,
+                            const ConvDims& d, int m_per_split, int ranges,
+                            hipStream_t stream) {
+    constexpr int lds = MG * WG_GROUP_BYTES;   // 147,456 B at MG = 4
+    static const bool attr_set = [] {
+        (void)hipFuncSetAttribute((const void*)&k_conv_wgrad<MG>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  lds);
+        return true;
+    }();
+    (void)attr_set;
+    const int zn = (ranges + MG - 1) / MG;
+    dim3 grid((unsigned)(d.K / 64), (unsigned)(d.R * d.S * d.C / 64),
+              (unsigned)zn);
+    k_conv_wgrad<MG><<<grid, CONV_THREADS * MG, lds, stream>>>(
+        (const uint16_t*)x, (const uint16_t*)dout, (float*)dw, d, m_per_split,
+        zn == 1);
 }
 
 extern "C" void launch_conv_wgrad(const void* x, const void* dout, void* dw,
@@ -401,13 +536,20 @@ extern "C" void launch_conv_wgrad(const void* x, const void* dout, void* dw,
         const int zn = (int)((M + mps - 1) / mps);
         dim3 grid((unsigned)(d.K / 128), (unsigned)(rsc / 128), (unsigned)zn);
         k_conv_wgrad8<<<grid, 512, 0, stream>>>(
-            (const uint16_t*)x, (const uint16_t*)dout, (float*)dw, d, mps);
+            (const uint16_t*)x, (const uint16_t*)dout, (float*)dw, d, mps,
+            zn == 1);
         return;
     }
     int m_per_split = (int)((M + n_splits - 1) / n_splits);
     m_per_split = (m_per_split + 2 * CONV_BK - 1) / (2 * CONV_BK) * (2 * CONV_BK);
-    const int zn = (int)((M + m_per_split - 1) / m_per_split);
-    dim3 grid((unsigned)(d.K / 64), (unsigned)(rsc / 64), (unsigned)zn);
-    k_conv_wgrad<<<grid, CONV_THREADS, 0, stream>>>(
-        (const uint16_t*)x, (const uint16_t*)dout, (float*)dw, d, m_per_split);
+    const int ranges = (int)((M + m_per_split - 1) / m_per_split);
+    const int tiles = (d.K / 64) * (rsc / 64);
+    int mg = wgrad_mg_forced();
+    if (!mg) mg = wgrad_pick_mg(tiles, ranges, m_per_split);
+    if (mg == 4)
+        launch_wgrad_mg<4>(x, dout, dw, d, m_per_split, ranges, stream);
+    else if (mg == 2)
+        launch_wgrad_mg<2>(x, dout, dw, d, m_per_split, ranges, stream);
+    else
+        launch_wgrad_mg<1>(x, dout, dw, d, m_per_split, ranges, stream);
 }
