@@ -58,7 +58,8 @@ class Solver(BaseSolver):
         self.register_stateful("model", "optim")
 
     def get_formatter(self, stage_name):
-        return Formatter({"acc": ".1%", "loss": ".5f"})
+        return Formatter({"acc": ".1%", "loss": ".5f", "lr": ".2e",
+                          "grad_norm": ".3f"})
 
     def _capture(self, shape):
         self._static_img = torch.zeros(shape, device=self.device)
@@ -108,6 +109,18 @@ class Solver(BaseSolver):
             self.optim.step()
         return loss, acc
 
+    def _optim_metrics(self):
+        """End-of-stage read-outs of the on-device schedule / clipping (one
+        host read each, here only): the lr the next step will use and the
+        last step's pre-clip gradient norm."""
+        out = {}
+        if getattr(self.optim, "schedule", None) is not None:
+            out["lr"] = self.optim.current_lr()
+        norm = getattr(self.optim, "last_grad_norm", None)
+        if norm is not None:
+            out["grad_norm"] = norm.item()
+        return out
+
     def do_train_valid(self, train: bool):
         stage = "train" if train else "valid"
         loader = self.loaders[stage]
@@ -119,6 +132,8 @@ class Solver(BaseSolver):
                 loss, acc = self._step(img, label, train)
                 metrics = avg({"loss": loss.item(), "acc": acc.item()})
                 lp.update(**metrics)
+        if train:
+            metrics.update(self._optim_metrics())
         if not math.isfinite(metrics["loss"]):
             # a NaN must halt the run loudly, not be silently averaged —
             # especially with graph capture in the loop

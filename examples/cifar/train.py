@@ -9,12 +9,34 @@ import torch
 import flashy_amd
 from flashy_amd import distrib
 from flashy_amd.models import native_resnet18, resnet18
-from flashy_amd.optim import FusedSGD
+from flashy_amd.optim import FusedSGD, MultiStep, WarmupCosine, WarmupLinear
 from flashy_amd import xp as fxp
 
 from .solver import Solver, SyntheticCIFAR
 
 main = fxp.entry_point("examples.cifar", Path(__file__).parent / "conf")
+
+
+def get_schedule(cfg, steps_per_epoch: int):
+    """The optional ``schedule:`` section -> an LRSchedule (None = off).
+    All lengths are in optimizer steps; ``total_steps`` defaults to the
+    whole run."""
+    section = cfg.get("schedule") or {}
+    kind = section.get("kind")
+    if kind is None:
+        return None
+    warmup = dict(warmup_steps=section.get("warmup_steps", 0),
+                  start_factor=section.get("start_factor", 0.0))
+    if kind == "multistep":
+        return MultiStep(section.get("milestones") or [],
+                         gamma=section.get("gamma", 0.1), **warmup)
+    klass = {"cosine": WarmupCosine, "linear": WarmupLinear}.get(kind)
+    if klass is None:
+        raise ValueError(f"schedule.kind must be cosine, linear or multistep, "
+                         f"got {kind!r}")
+    total = section.get("total_steps") or cfg.epochs * steps_per_epoch
+    return klass(total_steps=total, min_ratio=section.get("min_ratio", 0.0),
+                 **warmup)
 
 
 def get_solver(cfg):
@@ -24,10 +46,18 @@ def get_solver(cfg):
     if native:  # the gfx950 NHWC kernel path + flat fused optimizer
         model = native_resnet18(cfg.num_classes).to(device)
         distrib.broadcast_model(model)
+        loaders = _loaders(cfg)
+        # schedule and clipping run on the device inside optim.step(), so
+        # the captured step follows them under graph replay
         optim = FusedSGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
-                         weight_decay=cfg.weight_decay, bf16_mirror=True)
+                         weight_decay=cfg.weight_decay, bf16_mirror=True,
+                         schedule=get_schedule(cfg, len(loaders["train"])),
+                         max_grad_norm=cfg.get("max_grad_norm"))
         model.enable_wt_cache()
-        return Solver(cfg, model, _loaders(cfg), optim)
+        return Solver(cfg, model, loaders, optim)
+    if (cfg.get("schedule") or {}).get("kind") or cfg.get("max_grad_norm"):
+        raise ValueError("schedule / max_grad_norm need the native path "
+                         "(FusedSGD); this run uses torch.optim.SGD")
     model = resnet18(num_classes=cfg.num_classes, small_input=True).to(device)
     distrib.broadcast_model(model)
     optim = torch.optim.SGD(model.parameters(), lr=cfg.lr,

@@ -83,13 +83,18 @@ def _is_bf16(t: torch.Tensor) -> bool:
 
 def fused_sgd(p: torch.Tensor, g: torch.Tensor, m: tp.Optional[torch.Tensor],
               lr: float, momentum: float, wd: float, grad_scale: float = 1.0,
-              nesterov: bool = False, p_bf16: tp.Optional[torch.Tensor] = None) -> None:
+              nesterov: bool = False, p_bf16: tp.Optional[torch.Tensor] = None,
+              hyper: tp.Optional[torch.Tensor] = None) -> None:
+    """hyper: optional device block written by :func:`optim_prepare`; when
+    given, the kernel takes ``lr`` from it (the ``lr`` argument is ignored)
+    and multiplies ``grad_scale`` by its clip coefficient."""
     ext = require()
     assert p.is_contiguous() and g.is_contiguous()
     ext.fused_sgd(p.data_ptr(), g.data_ptr(),
                   m.data_ptr() if m is not None else 0,
                   p_bf16.data_ptr() if p_bf16 is not None else 0,
-                  p.numel(), lr, momentum, wd, grad_scale, nesterov, _stream())
+                  p.numel(), lr, momentum, wd, grad_scale, nesterov, _stream(),
+                  _hyper_ptr(hyper))
 
 
 def fused_adam(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
@@ -97,20 +102,92 @@ def fused_adam(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
                eps: float, wd: float, step: int, grad_scale: float = 1.0,
                adamw: bool = False,
                p_bf16: tp.Optional[torch.Tensor] = None,
-               step_dev: tp.Optional[torch.Tensor] = None) -> None:
+               step_dev: tp.Optional[torch.Tensor] = None,
+               hyper: tp.Optional[torch.Tensor] = None) -> None:
     """step_dev: optional int64 device scalar holding the step count — makes
-    the bias correction graph-replay-safe (advance it with adam_step_inc)."""
+    the bias correction graph-replay-safe (advance it with adam_step_inc).
+    hyper: as for :func:`fused_sgd`."""
     ext = require()
     assert p.is_contiguous() and g.is_contiguous()
     ext.fused_adam(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
                    p_bf16.data_ptr() if p_bf16 is not None else 0,
                    step_dev.data_ptr() if step_dev is not None else 0,
                    p.numel(), lr, beta1, beta2, eps, wd, step, grad_scale,
-                   adamw, _stream())
+                   adamw, _stream(), _hyper_ptr(hyper))
 
 
 def adam_step_inc(step_dev: torch.Tensor) -> None:
     require().adam_step_inc(step_dev.data_ptr(), _stream())
+
+
+# layout of the per-device hyper block (fp32), see csrc/fused_optim.hip
+HYPER_LR, HYPER_COEF, HYPER_NORM, HYPER_SIZE = 0, 1, 2, 4
+
+
+def _hyper_ptr(hyper: tp.Optional[torch.Tensor]) -> int:
+    if hyper is None:
+        return 0
+    assert hyper.dtype == torch.float32 and hyper.numel() >= HYPER_SIZE
+    assert hyper.is_cuda and hyper.is_contiguous()
+    return hyper.data_ptr()
+
+
+def grad_sqsum_blocks(n: int) -> int:
+    """Number of per-block partials :func:`grad_sqsum` writes for ``n``
+    elements."""
+    return require().grad_sqsum_blocks(n)
+
+
+def grad_sqsum(g: torch.Tensor, partials: torch.Tensor) -> int:
+    """Sum of squares of the flat fp32 buffer ``g`` into per-block fp32
+    partials (no atomics, no pre-zeroing: deterministic for a given size).
+    Returns how many leading elements of ``partials`` were written; feed
+    those to :func:`optim_prepare`."""
+    ext = require()
+    assert g.dtype == torch.float32 and partials.dtype == torch.float32
+    assert g.is_cuda and partials.is_cuda
+    assert g.is_contiguous() and partials.is_contiguous()
+    assert g.data_ptr() % 16 == 0, "float4 loads need a 16-byte aligned buffer"
+    blocks = ext.grad_sqsum_blocks(g.numel())
+    if partials.numel() < blocks:
+        raise ValueError(
+            f"partials holds {partials.numel()} floats, need {blocks}")
+    ext.grad_sqsum(g.data_ptr(), g.numel(), partials.data_ptr(), _stream())
+    return blocks
+
+
+def optim_prepare(hyper: torch.Tensor, schedule: tp.Any, base_lr: float,
+                  step_dev: tp.Optional[torch.Tensor] = None,
+                  partials: tp.Optional[torch.Tensor] = None,
+                  max_norm: float = 0.0) -> None:
+    """Write this step's ``lr`` / clip ``coef`` / gradient ``norm`` into the
+    device block ``hyper`` (one 1-block kernel, no host read).
+
+    schedule: an :class:`flashy_amd.optim.LRSchedule`; it is evaluated on the
+    device at ``step_dev - 1`` (``step_dev``: int64 device scalar holding the
+    1-based number of the step about to run; step 0 when absent).
+    partials: ALL of it is summed (pass exactly the slice that
+    :func:`grad_sqsum` wrote); ``None`` means no clipping: coef 1, norm 0."""
+    ext = require()
+    assert hyper.dtype == torch.float32 and hyper.numel() >= HYPER_SIZE
+    assert hyper.is_cuda and hyper.is_contiguous()
+    kind, warmup, start, total, floor, milestones, gamma = \
+        schedule.kernel_args()
+    n_partials = 0
+    if partials is not None:
+        assert partials.dtype == torch.float32 and partials.is_contiguous()
+        assert partials.is_cuda
+        if not max_norm > 0:
+            raise ValueError(f"max_norm must be > 0, got {max_norm}")
+        n_partials = partials.numel()
+    if step_dev is not None:
+        assert step_dev.dtype == torch.int64 and step_dev.is_cuda
+    ext.optim_prepare(hyper.data_ptr(),
+                      partials.data_ptr() if partials is not None else 0,
+                      n_partials,
+                      step_dev.data_ptr() if step_dev is not None else 0,
+                      float(max_norm), kind, float(base_lr), warmup, start,
+                      total, floor, list(milestones), gamma, _stream())
 
 
 def maxpool_fwd(x: torch.Tensor, y: torch.Tensor, argmax: torch.Tensor,

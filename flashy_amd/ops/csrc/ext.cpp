@@ -7,9 +7,11 @@
 
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
 
 #include <cstdint>
 #include <stdexcept>
+#include <vector>
 
 #include "conv8.h"   // ConvDims + the 8-wave plan/launch prototypes
 
@@ -77,12 +79,22 @@ void launch_bn_bwd_apply(const void* dz, const void* x, const void* work,
                          hipStream_t stream);
 void launch_fused_sgd(void* p, const void* g, void* m, void* p_bf16, int64_t n,
                       float lr, float momentum, float wd, float grad_scale,
-                      int nesterov, hipStream_t stream);
+                      int nesterov, const void* hyper, hipStream_t stream);
 void launch_fused_adam(void* p, const void* g, void* m, void* v, void* p_bf16,
                        void* step_dev, int64_t n, float lr, float beta1,
                        float beta2, float eps, float wd, int64_t step,
-                       float grad_scale, int adamw, hipStream_t stream);
+                       float grad_scale, int adamw, const void* hyper,
+                       hipStream_t stream);
 void launch_adam_step_inc(void* p, hipStream_t stream);
+int grad_sqsum_blocks(int64_t n);
+void launch_grad_sqsum(const void* g, int64_t n, void* partials,
+                       hipStream_t stream);
+void launch_optim_prepare(void* hyper, const void* partials, int n_partials,
+                          const void* step_dev, double max_norm, int kind,
+                          double base_lr, int64_t warmup_steps,
+                          double start_factor, int64_t total_steps,
+                          double min_ratio, const int64_t* milestones,
+                          int n_milestones, double gamma, hipStream_t stream);
 void launch_maxpool_fwd(const void* x, void* y, void* argmax, ConvDims d,
                         hipStream_t stream);
 void launch_maxpool_bwd(const void* dy, const void* argmax, void* dx,
@@ -336,31 +348,68 @@ PYBIND11_MODULE(_hip_ops, m) {
               check_last();
           });
 
+    // `hyper` (trailing, default 0): device block written by optim_prepare;
+    // when set, the kernel reads lr and the clip coefficient from it.
     m.def("fused_sgd",
           [](uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p_bf16,
              int64_t n, float lr, float momentum, float wd, float grad_scale,
-             bool nesterov, uintptr_t stream) {
+             bool nesterov, uintptr_t stream, uintptr_t hyper) {
               launch_fused_sgd((void*)p, (const void*)g, (void*)mom,
                                (void*)p_bf16, n, lr, momentum, wd, grad_scale,
-                               nesterov ? 1 : 0, as_stream(stream));
+                               nesterov ? 1 : 0, (const void*)hyper,
+                               as_stream(stream));
               check_last();
-          });
+          },
+          py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p_bf16"),
+          py::arg("n"), py::arg("lr"), py::arg("momentum"), py::arg("wd"),
+          py::arg("grad_scale"), py::arg("nesterov"), py::arg("stream"),
+          py::arg("hyper") = (uintptr_t)0);
 
     m.def("fused_adam",
           [](uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t var,
              uintptr_t p_bf16, uintptr_t step_dev, int64_t n, float lr,
              float beta1, float beta2, float eps, float wd, int64_t step,
-             float grad_scale, bool adamw, uintptr_t stream) {
+             float grad_scale, bool adamw, uintptr_t stream,
+             uintptr_t hyper) {
               launch_fused_adam((void*)p, (const void*)g, (void*)mom,
                                 (void*)var, (void*)p_bf16, (void*)step_dev, n,
                                 lr, beta1, beta2, eps, wd, step, grad_scale,
-                                adamw ? 1 : 0, as_stream(stream));
+                                adamw ? 1 : 0, (const void*)hyper,
+                                as_stream(stream));
               check_last();
-          });
+          },
+          py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("var"),
+          py::arg("p_bf16"), py::arg("step_dev"), py::arg("n"), py::arg("lr"),
+          py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("wd"),
+          py::arg("step"), py::arg("grad_scale"), py::arg("adamw"),
+          py::arg("stream"), py::arg("hyper") = (uintptr_t)0);
     m.def("adam_step_inc", [](uintptr_t p, uintptr_t stream) {
         launch_adam_step_inc((void*)p, as_stream(stream));
         check_last();
     });
+    m.def("grad_sqsum_blocks", [](int64_t n) { return grad_sqsum_blocks(n); });
+    m.def("grad_sqsum",
+          [](uintptr_t g, int64_t n, uintptr_t partials, uintptr_t stream) {
+              launch_grad_sqsum((const void*)g, n, (void*)partials,
+                                as_stream(stream));
+              check_last();
+          });
+    m.def("optim_prepare",
+          [](uintptr_t hyper, uintptr_t partials, int n_partials,
+             uintptr_t step_dev, double max_norm, int kind, double base_lr,
+             int64_t warmup_steps, double start_factor, int64_t total_steps,
+             double min_ratio, const std::vector<int64_t>& milestones,
+             double gamma, uintptr_t stream) {
+              if (milestones.size() > 8)
+                  throw std::invalid_argument("at most 8 milestones");
+              launch_optim_prepare((void*)hyper, (const void*)partials,
+                                   n_partials, (const void*)step_dev, max_norm,
+                                   kind, base_lr, warmup_steps, start_factor,
+                                   total_steps, min_ratio, milestones.data(),
+                                   (int)milestones.size(), gamma,
+                                   as_stream(stream));
+              check_last();
+          });
     m.def("maxpool_fwd",
           [](uintptr_t x, uintptr_t y, uintptr_t argmax, int N, int H, int W,
              int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,

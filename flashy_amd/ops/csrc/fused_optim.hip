@@ -14,6 +14,16 @@
 #include <math.h>
 
 // ---------------------------------------------------------------------------
+// Per-device "hyper" block: the step's effective learning rate and gradient
+// clip coefficient live in device memory, written by k_optim_prepare every
+// step and read by the update kernels.  A captured (HIP-graph) step therefore
+// follows an LR schedule and clips by global norm with no re-capture and no
+// host sync — the same idea as Adam's on-device step counter.
+// ---------------------------------------------------------------------------
+
+enum { HYPER_LR = 0, HYPER_COEF = 1, HYPER_NORM = 2, HYPER_SIZE = 4 };
+
+// ---------------------------------------------------------------------------
 // SGD (torch.optim.SGD semantics):
 //   d = g + wd * p
 //   if momentum: m = mu * m + d ; d = nesterov ? d + mu * m : m
@@ -28,6 +38,7 @@ struct SgdArgs {
     int64_t n;
     float lr, momentum, wd, grad_scale;
     int nesterov;
+    const float* hyper;  // device lr / clip coef (null = use lr by value)
 };
 
 __device__ __forceinline__ float sgd_one(const SgdArgs& a, float p, float g,
@@ -43,6 +54,10 @@ __device__ __forceinline__ float sgd_one(const SgdArgs& a, float p, float g,
 template <bool HAS_M, bool HAS_BF16>
 __global__ void __launch_bounds__(256)
 k_fused_sgd(SgdArgs a) {
+    if (a.hyper != nullptr) {
+        a.lr = a.hyper[HYPER_LR];
+        a.grad_scale *= a.hyper[HYPER_COEF];
+    }
     const int64_t n4 = a.n / 4;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     float4* p4 = reinterpret_cast<float4*>(a.p);
@@ -79,9 +94,9 @@ k_fused_sgd(SgdArgs a) {
 extern "C" void launch_fused_sgd(void* p, const void* g, void* m, void* p_bf16,
                                  int64_t n, float lr, float momentum, float wd,
                                  float grad_scale, int nesterov,
-                                 hipStream_t stream) {
+                                 const void* hyper, hipStream_t stream) {
     SgdArgs a{(float*)p, (const float*)g, (float*)m, (uint16_t*)p_bf16,
-              n, lr, momentum, wd, grad_scale, nesterov};
+              n, lr, momentum, wd, grad_scale, nesterov, (const float*)hyper};
     int grid = ew_grid(n / 4 + 1, 256, 1);
     if (m != nullptr && p_bf16 != nullptr)
         k_fused_sgd<true, true><<<grid, 256, 0, stream>>>(a);
@@ -106,6 +121,7 @@ struct AdamArgs {
     float* __restrict__ v;
     uint16_t* __restrict__ p_bf16;
     const long long* step_ptr;  // device step (graph-safe); null -> use bc1/bc2
+    const float* hyper;         // device lr / clip coef (null = use lr by value)
     int64_t n;
     float lr, beta1, beta2, eps, wd, bc1, bc2, grad_scale;
     int adamw;  // 1: decoupled weight decay, 0: L2 into grad
@@ -128,6 +144,10 @@ k_fused_adam(AdamArgs a) {
         const float t = (float)*a.step_ptr;
         a.bc1 = 1.f - powf(a.beta1, t);
         a.bc2 = 1.f - powf(a.beta2, t);
+    }
+    if (a.hyper != nullptr) {
+        a.lr = a.hyper[HYPER_LR];
+        a.grad_scale *= a.hyper[HYPER_COEF];
     }
     const int64_t n4 = a.n / 4;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -177,9 +197,11 @@ extern "C" void launch_fused_adam(void* p, const void* g, void* m, void* v,
                                   void* p_bf16, void* step_dev, int64_t n,
                                   float lr, float beta1, float beta2, float eps,
                                   float wd, int64_t step, float grad_scale,
-                                  int adamw, hipStream_t stream) {
+                                  int adamw, const void* hyper,
+                                  hipStream_t stream) {
     AdamArgs a{(float*)p, (const float*)g, (float*)m, (float*)v,
-               (uint16_t*)p_bf16, (const long long*)step_dev, n, lr, beta1,
+               (uint16_t*)p_bf16, (const long long*)step_dev,
+               (const float*)hyper, n, lr, beta1,
                beta2, eps, wd,
                1.f - powf(beta1, (float)step), 1.f - powf(beta2, (float)step),
                grad_scale, adamw};
@@ -188,4 +210,166 @@ extern "C" void launch_fused_adam(void* p, const void* g, void* m, void* v,
         k_fused_adam<true><<<grid, 256, 0, stream>>>(a);
     else
         k_fused_adam<false><<<grid, 256, 0, stream>>>(a);
+}
+
+// ---------------------------------------------------------------------------
+// Global gradient norm, pass 1: sum of squares of a flat fp32 buffer into one
+// partial per block.  Same float4 grid-stride shape and scalar tail as the
+// update kernels; no atomics and no pre-zeroing, so the result is
+// deterministic for a given n.  Each thread keeps four running sums (one per
+// float4 lane), so a running fp32 sum sees n / (4 * grid * 256) terms.
+// ---------------------------------------------------------------------------
+
+static inline int grad_sqsum_grid(int64_t n) {
+    return ew_grid(n / 4 + 1, 256, 1);
+}
+
+extern "C" int grad_sqsum_blocks(int64_t n) { return grad_sqsum_grid(n); }
+
+__global__ void __launch_bounds__(256)
+k_grad_sqsum(const float* __restrict__ g, int64_t n,
+             float* __restrict__ partials) {
+    const int64_t n4 = n / 4;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4 acc{0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const float4 v = g4[i];
+        acc.x += v.x * v.x;
+        acc.y += v.y * v.y;
+        acc.z += v.z * v.z;
+        acc.w += v.w * v.w;
+    }
+    // scalar tail
+    for (int64_t i = n4 * 4 + blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        const float v = g[i];
+        acc.x += v * v;
+    }
+    float sum = wave_sum((acc.x + acc.y) + (acc.z + acc.w));
+    __shared__ float wave_part[256 / WAVE_SIZE];
+    if ((threadIdx.x & (WAVE_SIZE - 1)) == 0)
+        wave_part[threadIdx.x / WAVE_SIZE] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partials[blockIdx.x] = (wave_part[0] + wave_part[1]) +
+                               (wave_part[2] + wave_part[3]);
+}
+
+extern "C" void launch_grad_sqsum(const void* g, int64_t n, void* partials,
+                                  hipStream_t stream) {
+    k_grad_sqsum<<<grad_sqsum_grid(n), 256, 0, stream>>>(
+        (const float*)g, n, (float*)partials);
+}
+
+// ---------------------------------------------------------------------------
+// Pass 2 (one block): sum the partials of every group on this device in
+// fixed order in fp64, derive the clip coefficient
+//   coef = min(1, max_norm / (norm + 1e-6))      (torch clip_grad_norm_)
+// and evaluate the LR schedule in closed form at the device step counter.
+// The schedule's parameters are constants of the run, so they travel by
+// value (frozen at graph capture, correctly).  The scalar math is fp64 in
+// one thread; only the stored lr / coef / norm are rounded to fp32.
+//
+//   warm(s)  = start + (1 - start) * s / W                   for s < W
+//   cosine   : floor + (1 - floor) * (1 + cos(pi * x)) / 2   x = (min(s,T)-W)/(T-W)
+//   linear   : floor + (1 - floor) * (1 - x)
+//   multistep: warm(s) * gamma ^ #{milestones <= s}
+// ---------------------------------------------------------------------------
+
+enum { SCHED_CONSTANT = 0, SCHED_COSINE = 1, SCHED_LINEAR = 2,
+       SCHED_MULTISTEP = 3 };
+
+#define SCHED_MAX_MILESTONES 8
+
+struct SchedArgs {
+    int kind;
+    int n_milestones;
+    long long warmup_steps;
+    long long total_steps;
+    long long milestones[SCHED_MAX_MILESTONES];
+    double base_lr, start_factor, min_ratio, gamma;
+};
+
+__device__ __forceinline__ double sched_factor(const SchedArgs& s,
+                                               long long step) {
+    if (s.kind == SCHED_CONSTANT) return 1.0;
+    if (step < 0) step = 0;
+    const bool in_warmup = step < s.warmup_steps;
+    const double warm = in_warmup
+        ? s.start_factor + (1.0 - s.start_factor) *
+              ((double)step / (double)s.warmup_steps)
+        : 1.0;
+    if (s.kind == SCHED_MULTISTEP) {
+        int passed = 0;
+        for (int i = 0; i < s.n_milestones; ++i)
+            passed += s.milestones[i] <= step ? 1 : 0;
+        return warm * pow(s.gamma, (double)passed);
+    }
+    if (in_warmup) return warm;
+    const long long t = (step < s.total_steps ? step : s.total_steps) -
+                        s.warmup_steps;
+    const double x = (double)t / (double)(s.total_steps - s.warmup_steps);
+    const double decay = s.kind == SCHED_COSINE
+        ? 0.5 * (1.0 + cos(3.14159265358979323846 * x))
+        : 1.0 - x;
+    return s.min_ratio + (1.0 - s.min_ratio) * decay;
+}
+
+__global__ void __launch_bounds__(256)
+k_optim_prepare(float* __restrict__ hyper, const float* __restrict__ partials,
+                int n_partials, const long long* __restrict__ step_ptr,
+                double max_norm, SchedArgs s) {
+    __shared__ double red[256];
+    double sq = 0.0;
+    if (partials != nullptr) {
+        double acc = 0.0;
+        for (int i = threadIdx.x; i < n_partials; i += 256)
+            acc += (double)partials[i];
+        red[threadIdx.x] = acc;
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if ((int)threadIdx.x < off)
+                red[threadIdx.x] += red[threadIdx.x + off];
+            __syncthreads();
+        }
+        sq = red[0];
+    }
+    if (threadIdx.x != 0) return;
+    double norm = 0.0, coef = 1.0;
+    if (partials != nullptr) {
+        norm = sqrt(sq);
+        const double c = max_norm / (norm + 1e-6);
+        coef = c > 1.0 ? 1.0 : c;  // a NaN norm stays NaN, as in torch
+    }
+    // the counter holds the 1-based number of the step about to run; the
+    // schedule is indexed from 0 (torch: scheduler.step() after optim.step())
+    const long long step = step_ptr != nullptr ? *step_ptr - 1 : 0;
+    hyper[HYPER_LR] = (float)(s.base_lr * sched_factor(s, step));
+    hyper[HYPER_COEF] = (float)coef;
+    hyper[HYPER_NORM] = (float)norm;
+}
+
+extern "C" void launch_optim_prepare(void* hyper, const void* partials,
+                                     int n_partials, const void* step_dev,
+                                     double max_norm, int kind, double base_lr,
+                                     int64_t warmup_steps, double start_factor,
+                                     int64_t total_steps, double min_ratio,
+                                     const int64_t* milestones,
+                                     int n_milestones, double gamma,
+                                     hipStream_t stream) {
+    SchedArgs s{};
+    s.kind = kind;
+    s.n_milestones = n_milestones < SCHED_MAX_MILESTONES
+        ? n_milestones : SCHED_MAX_MILESTONES;
+    s.warmup_steps = warmup_steps;
+    s.total_steps = total_steps;
+    for (int i = 0; i < s.n_milestones; ++i) s.milestones[i] = milestones[i];
+    s.base_lr = base_lr;
+    s.start_factor = start_factor;
+    s.min_ratio = min_ratio;
+    s.gamma = gamma;
+    k_optim_prepare<<<1, 256, 0, stream>>>(
+        (float*)hyper, (const float*)partials, n_partials,
+        (const long long*)step_dev, max_norm, s);
 }

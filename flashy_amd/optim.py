@@ -20,9 +20,18 @@ Replaces the reference's use of torch.optim.SGD/Adam in its workloads
 On CUDA devices the native extension is REQUIRED (loud failure otherwise);
 on CPU the same classes run a torch fallback with identical numerics, so
 every test runs in CI.
+
+Learning-rate schedules and global-norm gradient clipping are part of
+``step()`` (``schedule=`` / ``max_grad_norm=``): the effective ``lr`` and the
+clip coefficient are computed ON THE DEVICE each step from a device step
+counter and the gradient arena, and the update kernels read them from
+memory.  A step captured into a HIP graph therefore follows the schedule and
+clips, with no re-capture and no host sync.  :class:`LRSchedule` objects are
+the host mirror of the same closed forms.
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import typing as tp
 
@@ -31,6 +40,135 @@ import torch
 from . import ops
 
 ParamsT = tp.Iterable[torch.nn.Parameter]
+
+MAX_MILESTONES = 8
+
+
+# ---------------------------------------------------------------------------
+# LR schedules: closed forms of the step index (0 for the first step() call).
+# The device evaluates the same expressions in k_optim_prepare
+# (ops/csrc/fused_optim.hip); `kernel_args` is the POD that travels there.
+# ---------------------------------------------------------------------------
+
+class LRSchedule:
+    """Immutable description of a learning-rate schedule.
+
+    ``lr_at(step, base_lr)`` is the learning rate used by the ``step``-th
+    update counted from 0 — torch's convention of calling
+    ``scheduler.step()`` after ``optimizer.step()``.  Plain Python floats:
+    this is the CPU path, the host mirror for logging, and what the tests
+    compare the device against."""
+
+    KIND = 0
+
+    def factor(self, step: int) -> float:
+        del step
+        return 1.0
+
+    def lr_at(self, step: int, base_lr: float) -> float:
+        return base_lr * self.factor(max(int(step), 0))
+
+    def _warm(self, step: int) -> float:
+        if step >= self.warmup_steps:
+            return 1.0
+        return self.start_factor + (1.0 - self.start_factor) * (
+            step / self.warmup_steps)
+
+    def _check_warmup(self) -> None:
+        if self.warmup_steps < 0:
+            raise ValueError(f"warmup_steps must be >= 0: {self.warmup_steps}")
+        if self.start_factor < 0:
+            raise ValueError(f"start_factor must be >= 0: {self.start_factor}")
+
+    def kernel_args(self) -> tp.Tuple[tp.Any, ...]:
+        """(kind, warmup_steps, start_factor, total_steps, min_ratio,
+        milestones, gamma) as plain ints / floats."""
+        def get(name: str, default: tp.Any) -> tp.Any:
+            return getattr(self, name, default)
+
+        return (self.KIND, int(get("warmup_steps", 0)),
+                float(get("start_factor", 0.0)), int(get("total_steps", 1)),
+                float(get("min_ratio", 0.0)),
+                tuple(int(m) for m in get("milestones", ())),
+                float(get("gamma", 1.0)))
+
+
+@dataclasses.dataclass(frozen=True)
+class Constant(LRSchedule):
+    """``lr`` stays at the base value."""
+    KIND = 0
+
+
+@dataclasses.dataclass(frozen=True)
+class _WarmupDecay(LRSchedule):
+    warmup_steps: int
+    total_steps: int
+    min_ratio: float = 0.0
+    start_factor: float = 0.0
+
+    def __post_init__(self):
+        self._check_warmup()
+        if self.total_steps <= self.warmup_steps:
+            raise ValueError(
+                f"total_steps ({self.total_steps}) must exceed warmup_steps "
+                f"({self.warmup_steps})")
+
+    def _decay(self, x: float) -> float:
+        raise NotImplementedError
+
+    def factor(self, step: int) -> float:
+        if step < self.warmup_steps:
+            return self._warm(step)
+        t = min(step, self.total_steps) - self.warmup_steps
+        x = t / (self.total_steps - self.warmup_steps)
+        return self.min_ratio + (1.0 - self.min_ratio) * self._decay(x)
+
+
+@dataclasses.dataclass(frozen=True)
+class WarmupCosine(_WarmupDecay):
+    """Linear warmup from ``start_factor`` to 1 over ``warmup_steps``, then a
+    half cosine down to ``min_ratio`` at ``total_steps``; the floor holds
+    afterwards."""
+    KIND = 1
+
+    def _decay(self, x: float) -> float:
+        return 0.5 * (1.0 + math.cos(math.pi * x))
+
+
+@dataclasses.dataclass(frozen=True)
+class WarmupLinear(_WarmupDecay):
+    """Linear warmup, then a straight line down to ``min_ratio`` at
+    ``total_steps``; the floor holds afterwards."""
+    KIND = 2
+
+    def _decay(self, x: float) -> float:
+        return 1.0 - x
+
+
+@dataclasses.dataclass(frozen=True)
+class MultiStep(LRSchedule):
+    """``lr`` is multiplied by ``gamma`` at each milestone (at most 8), on top
+    of an optional linear warmup."""
+    KIND = 3
+    milestones: tp.Sequence[int]
+    gamma: float = 0.1
+    warmup_steps: int = 0
+    start_factor: float = 0.0
+
+    def __post_init__(self):
+        object.__setattr__(self, "milestones",
+                           tuple(int(m) for m in self.milestones))
+        if len(self.milestones) > MAX_MILESTONES:
+            raise ValueError(
+                f"at most {MAX_MILESTONES} milestones, got "
+                f"{len(self.milestones)}")
+        if any(m < 0 for m in self.milestones):
+            raise ValueError(f"milestones must be >= 0: {self.milestones}")
+        self._check_warmup()
+
+    def factor(self, step: int) -> float:
+        passed = sum(1 for m in self.milestones if m <= step)
+        return self._warm(step) * math.pow(self.gamma, float(passed))
 
 
 class _Group:
@@ -85,7 +223,14 @@ class FlatOptimizer:
     """Base: flat parameter/grad packing + state dict plumbing."""
 
     def __init__(self, params: ParamsT, defaults: tp.Dict[str, tp.Any],
-                 bf16_mirror: bool = False):
+                 bf16_mirror: bool = False,
+                 schedule: tp.Optional[LRSchedule] = None,
+                 max_grad_norm: tp.Optional[float] = None):
+        if schedule is not None and not isinstance(schedule, LRSchedule):
+            raise TypeError(f"schedule must be an LRSchedule, got {schedule!r}")
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(
+                f"max_grad_norm must be > 0 or None, got {max_grad_norm}")
         params = [p for p in params if p.requires_grad]
         if not params:
             raise ValueError("no trainable parameters")
@@ -102,6 +247,117 @@ class FlatOptimizer:
         self._use_hip = any(g.device.type == "cuda" for g in self.groups)
         if self._use_hip:
             ops.require()  # fail loudly now, not at the first step
+        # device step counters (one int64 per CUDA device), created by the
+        # subclasses that need one; each holds the 1-based number of the
+        # NEXT step, and is authoritative under HIP-graph replay
+        self._step_dev: tp.Dict[torch.device, torch.Tensor] = {}
+        self.schedule = schedule
+        self.max_grad_norm = max_grad_norm
+        # "managed" step: lr / clip coefficient come from a per-device hyper
+        # block (CUDA) or from _host_hyper (CPU) instead of defaults["lr"]
+        self._managed = schedule is not None or max_grad_norm is not None
+        self._sched = schedule if schedule is not None else Constant()
+        self._hyper: tp.Dict[torch.device, torch.Tensor] = {}
+        self._partials: tp.Dict[torch.device, torch.Tensor] = {}
+        self._partial_slices: tp.Dict[int, torch.Tensor] = {}
+        self._host_hyper: tp.Tuple[float, tp.Optional[float]] = (0.0, None)
+        self._host_norm: tp.Optional[torch.Tensor] = None
+        if self._managed:
+            self._init_managed()
+
+    def _init_managed(self) -> None:
+        devices = []
+        for g in self.groups:
+            if g.device not in devices:
+                devices.append(g.device)
+        clip = self.max_grad_norm is not None
+        if clip and len(devices) > 1:
+            raise NotImplementedError(
+                "max_grad_norm with parameters on more than one device: a "
+                "cross-device gradient norm is not implemented")
+        for dev in devices:
+            if dev.type != "cuda":
+                if clip:
+                    self._host_norm = torch.zeros((), dtype=torch.float32)
+                continue
+            hyper = torch.zeros(ops.HYPER_SIZE, dtype=torch.float32, device=dev)
+            hyper[ops.HYPER_LR] = self.defaults["lr"]
+            hyper[ops.HYPER_COEF] = 1.0
+            self._hyper[dev] = hyper
+            if not clip:
+                continue
+            mine = [g for g in self.groups if g.device == dev]
+            counts = [ops.grad_sqsum_blocks(g.flat_g.numel()) for g in mine]
+            ws = torch.zeros(sum(counts), dtype=torch.float32, device=dev)
+            self._partials[dev] = ws
+            offset = 0
+            for g, n in zip(mine, counts):
+                self._partial_slices[id(g)] = ws[offset:offset + n]
+                offset += n
+
+    def _make_step_counters(self) -> None:
+        for g in self.groups:
+            if g.device.type == "cuda" and g.device not in self._step_dev:
+                self._step_dev[g.device] = torch.ones(
+                    1, dtype=torch.int64, device=g.device)
+
+    def _steps_done(self) -> int:
+        """Number of completed steps; the device counter is authoritative
+        (under graph replay the host count freezes).  Reads the device."""
+        if self._step_dev:
+            return max(int(s.item()) for s in self._step_dev.values()) - 1
+        return self.step_count
+
+    def current_lr(self) -> float:
+        """Learning rate the next ``step()`` will use (host mirror of the
+        schedule at the authoritative step count) — what
+        ``scheduler.get_last_lr()`` reports in a torch loop."""
+        return self._sched.lr_at(self._steps_done(), self.defaults["lr"])
+
+    @property
+    def last_grad_norm(self) -> tp.Optional[torch.Tensor]:
+        """Pre-clip global gradient norm of the last step as a 0-dim tensor
+        on the parameters' device (no sync; call ``.item()`` when logging).
+        ``None`` unless ``max_grad_norm`` is set."""
+        if self.max_grad_norm is None:
+            return None
+        for hyper in self._hyper.values():
+            return hyper[ops.HYPER_NORM]
+        return self._host_norm
+
+    def _prepare(self) -> None:
+        """Norm pass (only when clipping) + the 1-block prepare kernel per
+        device; on CPU the same math in Python floats.  Stream-ordered, no
+        host reads of device memory: capturable."""
+        clip = self.max_grad_norm is not None
+        base_lr = self.defaults["lr"]
+        for dev, hyper in self._hyper.items():
+            if clip:
+                for g in self.groups:
+                    if g.device == dev:
+                        ops.grad_sqsum(g.flat_g, self._partial_slices[id(g)])
+            ops.optim_prepare(hyper, self._sched, base_lr,
+                              step_dev=self._step_dev.get(dev),
+                              partials=self._partials.get(dev),
+                              max_norm=self.max_grad_norm if clip else 0.0)
+        if len(self._hyper) == len({g.device for g in self.groups}):
+            return
+        coef = None
+        if clip:
+            sq = sum(float(g.flat_g.double().pow(2).sum())
+                     for g in self.groups if g.device.type != "cuda")
+            norm = math.sqrt(sq)
+            c = self.max_grad_norm / (norm + 1e-6)
+            coef = 1.0 if c > 1.0 else c  # a NaN norm stays NaN, as in torch
+            self._host_norm.fill_(norm)
+        self._host_hyper = (
+            self._sched.lr_at(self.step_count - 1, base_lr), coef)
+
+    def _lr_coef(self) -> tp.Tuple[float, tp.Optional[float]]:
+        """(lr, clip coefficient or None) for the CPU fallback."""
+        if self._managed:
+            return self._host_hyper
+        return self.defaults["lr"], None
 
     # -- torch-optimizer-compatible surface ---------------------------------
     def zero_grad(self, set_to_none: bool = False) -> None:
@@ -128,8 +384,12 @@ class FlatOptimizer:
     def step(self, closure: tp.Optional[tp.Callable] = None) -> None:
         loss = closure() if closure is not None else None
         self.step_count += 1
+        if self._managed:
+            self._prepare()
         for g in self.groups:
             self._step_group(g)
+        for dev_step in self._step_dev.values():
+            ops.adam_step_inc(dev_step)
         return loss
 
     def _step_group(self, group: _Group) -> None:
@@ -143,6 +403,10 @@ class FlatOptimizer:
         del state
 
     def state_dict(self) -> tp.Dict[str, tp.Any]:
+        # The device counter is authoritative: under HIP-graph capture
+        # step() runs only at capture time, so the host count freezes
+        # while the device counter advances per replay.
+        self.step_count = self._steps_done()
         return {
             "defaults": dict(self.defaults),
             "step_count": self.step_count,
@@ -153,6 +417,8 @@ class FlatOptimizer:
         self.defaults.update(state.get("defaults", {}))
         self.step_count = state.get("step_count", 0)
         self._load_extra_state(state.get("extra", {}))
+        for dev_step in self._step_dev.values():
+            dev_step.fill_(self.step_count + 1)
         # model params are usually restored in the same breath
         # (StateManager restores the model first); re-sync the bf16 mirrors
         self.refresh_bf16()
@@ -164,12 +430,19 @@ class FusedSGD(FlatOptimizer):
 
     def __init__(self, params: ParamsT, lr: float, momentum: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False,
-                 bf16_mirror: bool = False):
+                 bf16_mirror: bool = False,
+                 schedule: tp.Optional[LRSchedule] = None,
+                 max_grad_norm: tp.Optional[float] = None):
         super().__init__(params, dict(lr=lr, momentum=momentum,
                                       weight_decay=weight_decay,
-                                      nesterov=nesterov), bf16_mirror)
+                                      nesterov=nesterov), bf16_mirror,
+                         schedule, max_grad_norm)
         self._momentum_buffers = [
             g.buffers_like() if momentum != 0 else None for g in self.groups]
+        if schedule is not None:
+            # the schedule is evaluated on the device from this counter, so
+            # a captured step keeps following it under replay
+            self._make_step_counters()
 
     def _step_group(self, group: _Group) -> None:
         d = self.defaults
@@ -177,17 +450,21 @@ class FusedSGD(FlatOptimizer):
         if group.device.type == "cuda":
             ops.fused_sgd(group.flat_p, group.flat_g, m, d["lr"],
                           d["momentum"], d["weight_decay"],
-                          nesterov=d["nesterov"], p_bf16=group.flat_p16)
+                          nesterov=d["nesterov"], p_bf16=group.flat_p16,
+                          hyper=self._hyper.get(group.device))
             return
         # CPU fallback, identical math
+        lr, coef = self._lr_coef()
         with torch.no_grad():
             g = group.flat_g
+            if coef is not None:
+                g = g * coef
             if d["weight_decay"] != 0:
                 g = g.add(group.flat_p, alpha=d["weight_decay"])
             if d["momentum"] != 0:
                 m.mul_(d["momentum"]).add_(g)
                 g = g.add(m, alpha=d["momentum"]) if d["nesterov"] else m
-            group.flat_p.add_(g, alpha=-d["lr"])
+            group.flat_p.add_(g, alpha=-lr)
             group.refresh_bf16()
 
     def _extra_state(self):
@@ -207,20 +484,20 @@ class FusedAdam(FlatOptimizer):
     def __init__(self, params: ParamsT, lr: float = 1e-3,
                  betas: tp.Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.0,
-                 adamw: bool = False, bf16_mirror: bool = False):
+                 adamw: bool = False, bf16_mirror: bool = False,
+                 schedule: tp.Optional[LRSchedule] = None,
+                 max_grad_norm: tp.Optional[float] = None):
         super().__init__(params, dict(lr=lr, beta1=betas[0], beta2=betas[1],
                                       eps=eps, weight_decay=weight_decay,
-                                      adamw=adamw), bf16_mirror)
+                                      adamw=adamw), bf16_mirror,
+                         schedule, max_grad_norm)
         self._exp_avg = [g.buffers_like() for g in self.groups]
         self._exp_avg_sq = [g.buffers_like() for g in self.groups]
         # device-side step counter: the kernel reads it for bias correction,
         # so the whole step is HIP-graph-replay-safe (a captured host step
         # count would freeze).  Starts at 1 = the value used by step #1.
-        self._step_dev = {}
-        for g in self.groups:
-            if g.device.type == "cuda" and g.device not in self._step_dev:
-                self._step_dev[g.device] = torch.ones(
-                    1, dtype=torch.int64, device=g.device)
+        # A schedule reads the same counter (at index count - 1).
+        self._make_step_counters()
 
     def _step_group(self, group: _Group) -> None:
         d = self.defaults
@@ -231,13 +508,17 @@ class FusedAdam(FlatOptimizer):
                            d["beta1"], d["beta2"], d["eps"],
                            d["weight_decay"], self.step_count,
                            adamw=d["adamw"], p_bf16=group.flat_p16,
-                           step_dev=self._step_dev[group.device])
+                           step_dev=self._step_dev[group.device],
+                           hyper=self._hyper.get(group.device))
             return
+        lr, coef = self._lr_coef()
         with torch.no_grad():
             g = group.flat_g
             p = group.flat_p
+            if coef is not None:
+                g = g * coef
             if d["adamw"]:
-                p.mul_(1 - d["lr"] * d["weight_decay"])
+                p.mul_(1 - lr * d["weight_decay"])
             elif d["weight_decay"] != 0:
                 g = g.add(p, alpha=d["weight_decay"])
             m.mul_(d["beta1"]).add_(g, alpha=1 - d["beta1"])
@@ -245,24 +526,8 @@ class FusedAdam(FlatOptimizer):
             bc1 = 1 - d["beta1"] ** self.step_count
             bc2 = 1 - d["beta2"] ** self.step_count
             denom = (v / bc2).sqrt_().add_(d["eps"])
-            p.addcdiv_(m / bc1, denom, value=-d["lr"])
+            p.addcdiv_(m / bc1, denom, value=-lr)
             group.refresh_bf16()
-
-    def step(self, closure=None):
-        out = super().step(closure)
-        for dev_step in self._step_dev.values():
-            ops.adam_step_inc(dev_step)
-        return out
-
-    def state_dict(self):
-        if self._step_dev:
-            # The device counter is authoritative: under HIP-graph capture
-            # step() runs only at capture time, so the host count freezes
-            # while the device counter advances per replay.  It holds the
-            # NEXT step number (starts at 1 before step #1).
-            self.step_count = max(
-                int(s.item()) for s in self._step_dev.values()) - 1
-        return super().state_dict()
 
     def _extra_state(self):
         return {"exp_avg": self._exp_avg, "exp_avg_sq": self._exp_avg_sq}
@@ -272,5 +537,3 @@ class FusedAdam(FlatOptimizer):
             mine.copy_(got.to(mine.device))
         for mine, got in zip(self._exp_avg_sq, state.get("exp_avg_sq", [])):
             mine.copy_(got.to(mine.device))
-        for dev_step in self._step_dev.values():
-            dev_step.fill_(self.step_count + 1)
