@@ -14,6 +14,7 @@ import torch
 from torch.nn import functional as F
 
 from flashy_amd import BaseSolver, Formatter, distrib
+from flashy_amd.data import DeviceAugment
 from flashy_amd.functional import accuracy, cross_entropy
 from flashy_amd.graph import CapturedStep
 from flashy_amd.models.resnet_native import NativeResNet
@@ -22,12 +23,18 @@ from flashy_amd.utils import averager
 
 class SyntheticCIFAR:
     """Deterministic CIFAR-10-shaped dataset: sample i is seeded noise with a
-    class-dependent mean, so accuracy is learnable above chance."""
+    class-dependent mean, so accuracy is learnable above chance.
 
-    def __init__(self, size: int, num_classes: int = 10, train: bool = True):
+    ``uint8=True`` yields the same seeded image as a decoder would hand it
+    over: uint8 HWC ``[32, 32, 3]``, quantized as ``round(img * 64 + 128)``
+    clamped to 0..255 (the input of :class:`flashy_amd.data.DeviceAugment`)."""
+
+    def __init__(self, size: int, num_classes: int = 10, train: bool = True,
+                 uint8: bool = False):
         self.size = size
         self.num_classes = num_classes
         self.offset = 0 if train else 1 << 24
+        self.uint8 = uint8
 
     def __len__(self):
         return self.size
@@ -36,6 +43,9 @@ class SyntheticCIFAR:
         g = torch.Generator().manual_seed(index + self.offset)
         label = int(torch.randint(self.num_classes, (1,), generator=g))
         img = torch.randn(3, 32, 32, generator=g) * 0.5 + label * 0.1
+        if self.uint8:
+            img = (img * 64 + 128).round().clamp(0, 255).to(torch.uint8)
+            img = img.permute(1, 2, 0).contiguous()
         return img, label
 
 
@@ -56,25 +66,57 @@ class Solver(BaseSolver):
                           and not distrib.is_distributed())
         self._graph = None
         self.register_stateful("model", "optim")
+        # optional on-device ingest: uint8 NHWC batches -> crop / flip /
+        # normalize -> bf16 NHWC.  Its step counter lives on the device and
+        # is checkpointed, so a resumed run continues the augmentation stream.
+        self.augment = None
+        section = cfg.get("augment") or {}
+        if section.get("enabled", False):
+            self.augment = DeviceAugment(
+                32, pad=section.get("pad", 4), flip=section.get("flip", 0.5),
+                mean=tuple(section.get("mean", (0., 0., 0.))),
+                std=tuple(section.get("std", (1., 1., 1.))),
+                seed=cfg.seed, device=self.device)
+            self.register_stateful("augment")
 
     def get_formatter(self, stage_name):
         return Formatter({"acc": ".1%", "loss": ".5f", "lr": ".2e",
                           "grad_norm": ".3f"})
 
+    def _ingest(self, img, train: bool):
+        """uint8 NHWC device batch -> model input.  The native model takes
+        the bf16 NHWC output as is; the torch model (CPU runs, native=false)
+        gets it as fp32 NCHW."""
+        x = self.augment(img, train=train)
+        if not self.native:
+            x = x.permute(0, 3, 1, 2).float()
+        return x
+
     def _capture(self, shape):
-        self._static_img = torch.zeros(shape, device=self.device)
+        self._static_img = torch.zeros(
+            shape, device=self.device,
+            dtype=torch.uint8 if self.augment is not None else None)
         self._static_label = torch.zeros(shape[0], dtype=torch.long,
                                          device=self.device)
 
         def step():
             self.optim.zero_grad(set_to_none=False)
-            est = self.model(self._static_img)
+            x = self._static_img
+            if self.augment is not None:
+                # ingest + counter bump are part of the graph: every replay
+                # reads the advanced counter and crops differently
+                x = self._ingest(x, True)
+            est = self.model(x)
             loss = cross_entropy(est, self._static_label)
             loss.backward()
             self.optim.step()
             return loss, est
 
+        drawn = self.augment.state_dict() if self.augment is not None else None
         self._graph = CapturedStep(step, warmup=3).capture()
+        if drawn is not None:
+            # the warmup steps ran on the zero buffer: give their draws back
+            self.augment.load_state_dict(drawn)
 
     def _graphed_step(self, img, label):
         """One training step as a single hipGraph replay (static buffers)."""
@@ -92,6 +134,8 @@ class Solver(BaseSolver):
             return self._graphed_step(img, label)
         img = img.to(self.device, non_blocking=True)
         label = label.to(self.device, non_blocking=True)
+        if self.augment is not None:
+            img = self._ingest(img, train)
         with torch.autocast("cuda", torch.bfloat16, enabled=self.autocast):
             est = self.model(img)
         if self.native and train:

@@ -66,11 +66,15 @@ def get_solver(cfg):
 
 
 def _loaders(cfg):
+    # augment.enabled: samples travel as uint8 HWC and the solver's
+    # DeviceAugment turns them into the model's input on the device
+    uint8 = bool((cfg.get("augment") or {}).get("enabled", False))
     return {
-        "train": distrib.loader(SyntheticCIFAR(cfg.dataset_size, cfg.num_classes),
+        "train": distrib.loader(SyntheticCIFAR(cfg.dataset_size, cfg.num_classes,
+                                               uint8=uint8),
                                 batch_size=cfg.batch_size, shuffle=True),
         "valid": distrib.loader(SyntheticCIFAR(cfg.valid_size, cfg.num_classes,
-                                               train=False),
+                                               train=False, uint8=uint8),
                                 batch_size=cfg.batch_size, shuffle=False),
     }
 

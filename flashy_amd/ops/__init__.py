@@ -190,6 +190,49 @@ def optim_prepare(hyper: torch.Tensor, schedule: tp.Any, base_lr: float,
                       total, floor, list(milestones), gamma, _stream())
 
 
+# ---------------------------------------------------------------------------
+# input ingest (uint8 NHWC -> bf16 NHWC; see flashy_amd/data.py)
+# ---------------------------------------------------------------------------
+
+def image_ingest(src: torch.Tensor, out: torch.Tensor,
+                 step_dev: tp.Optional[torch.Tensor], seed: int, pad: int,
+                 p_flip: float, scale: tp.Sequence[float],
+                 bias: tp.Sequence[float], fill: int = 0,
+                 train: bool = True) -> None:
+    """Fused crop / horizontal flip / normalize: uint8 NHWC ``src``
+    [N, H, W, 3] -> bf16 NHWC ``out`` [N, OH, OW, 3], one launch.
+
+    Train mode draws each sample's crop offset and flip bit from a hash of
+    (``seed``, ``step_dev``, sample index) and then advances ``step_dev``
+    (int64 device scalar) by one on the same stream, so a captured step
+    augments differently on every replay.  Eval mode is the centre crop
+    without flip; ``step_dev`` is neither read nor advanced.  ``scale`` /
+    ``bias`` are the per-channel fp32 values of ``u8 * scale + bias``."""
+    ext = require()
+    assert src.dtype == torch.uint8 and out.dtype == torch.bfloat16
+    assert src.is_cuda and out.is_cuda and src.device == out.device
+    assert src.is_contiguous() and out.is_contiguous()
+    assert src.dim() == 4 and out.dim() == 4, (src.shape, out.shape)
+    N, H, W, C = src.shape
+    OH, OW = out.shape[1], out.shape[2]
+    assert C == 3 and out.shape[0] == N and out.shape[3] == 3, \
+        (src.shape, out.shape)
+    assert pad >= 0 and 1 <= OH <= H + 2 * pad and 1 <= OW <= W + 2 * pad, \
+        (src.shape, out.shape, pad)
+    assert len(scale) == 3 and len(bias) == 3
+    assert 0 <= fill <= 255 and 0.0 <= p_flip <= 1.0
+    if train:
+        assert step_dev is not None and step_dev.dtype == torch.int64
+        assert step_dev.is_cuda and step_dev.numel() == 1
+    ext.image_ingest(src.data_ptr(), out.data_ptr(),
+                     step_dev.data_ptr() if train else 0, N, H, W, OH, OW,
+                     pad, seed & (2 ** 64 - 1), round(p_flip * 2 ** 24),
+                     [float(s) for s in scale], [float(b) for b in bias],
+                     fill, train, _stream())
+    if train:
+        ext.adam_step_inc(step_dev.data_ptr(), _stream())
+
+
 def maxpool_fwd(x: torch.Tensor, y: torch.Tensor, argmax: torch.Tensor,
                 d: "ConvDims") -> None:
     assert d.C % 8 == 0

@@ -95,6 +95,11 @@ void launch_optim_prepare(void* hyper, const void* partials, int n_partials,
                           double start_factor, int64_t total_steps,
                           double min_ratio, const int64_t* milestones,
                           int n_milestones, double gamma, hipStream_t stream);
+void launch_image_ingest(const void* src, void* out, const void* step_dev,
+                         int N, int H, int W, int OH, int OW, int pad,
+                         uint64_t seed, uint32_t flip_thresh,
+                         const float* scale, const float* bias, int fill,
+                         int train, hipStream_t stream);
 void launch_maxpool_fwd(const void* x, void* y, void* argmax, ConvDims d,
                         hipStream_t stream);
 void launch_maxpool_bwd(const void* dy, const void* argmax, void* dx,
@@ -408,6 +413,24 @@ PYBIND11_MODULE(_hip_ops, m) {
                                    total_steps, min_ratio, milestones.data(),
                                    (int)milestones.size(), gamma,
                                    as_stream(stream));
+              check_last();
+          });
+    // uint8 NHWC -> bf16 NHWC crop / flip / normalize (csrc/ingest.hip);
+    // step_dev = 0 is allowed in eval mode only (train = false)
+    m.def("image_ingest",
+          [](uintptr_t src, uintptr_t out, uintptr_t step_dev, int N, int H,
+             int W, int OH, int OW, int pad, uint64_t seed,
+             uint32_t flip_thresh, const std::vector<float>& scale,
+             const std::vector<float>& bias, int fill, bool train,
+             uintptr_t stream) {
+              if (scale.size() != 3 || bias.size() != 3)
+                  throw std::invalid_argument("scale and bias take 3 values");
+              if (train && step_dev == 0)
+                  throw std::invalid_argument("train mode needs step_dev");
+              launch_image_ingest((const void*)src, (void*)out,
+                                  (const void*)step_dev, N, H, W, OH, OW, pad,
+                                  seed, flip_thresh, scale.data(), bias.data(),
+                                  fill, train, as_stream(stream));
               check_last();
           });
     m.def("maxpool_fwd",
