@@ -14,7 +14,7 @@ import torch
 from torch.nn import functional as F
 
 from flashy_amd import BaseSolver, Formatter, distrib
-from flashy_amd.data import DeviceAugment
+from flashy_amd.data import DeviceAugment, DeviceResizedCrop
 from flashy_amd.functional import accuracy, cross_entropy
 from flashy_amd.graph import CapturedStep
 from flashy_amd.models.resnet_native import NativeResNet
@@ -49,6 +49,26 @@ class SyntheticCIFAR:
         return img, label
 
 
+def make_augment(section, seed: int, device):
+    """The on-device ingest the ``augment`` config section asks for, or
+    None when it is off: :class:`DeviceAugment` (crop with padding), or
+    :class:`DeviceResizedCrop` when ``augment.resized_crop`` is set — to
+    ``true`` for the defaults, or to a section with ``scale`` / ``ratio``."""
+    if not section.get("enabled", False):
+        return None
+    common = dict(flip=section.get("flip", 0.5),
+                  mean=tuple(section.get("mean", (0., 0., 0.))),
+                  std=tuple(section.get("std", (1., 1., 1.))),
+                  seed=seed, device=device)
+    resized = section.get("resized_crop", False)
+    if not resized:
+        return DeviceAugment(32, pad=section.get("pad", 4), **common)
+    opts = resized if isinstance(resized, dict) else {}
+    return DeviceResizedCrop(32, scale=tuple(opts.get("scale", (0.08, 1.0))),
+                             ratio=tuple(opts.get("ratio", (3 / 4, 4 / 3))),
+                             **common)
+
+
 class Solver(BaseSolver):
     def __init__(self, cfg, model, loaders, optim):
         super().__init__()
@@ -69,15 +89,13 @@ class Solver(BaseSolver):
         # optional on-device ingest: uint8 NHWC batches -> crop / flip /
         # normalize -> bf16 NHWC.  Its step counter lives on the device and
         # is checkpointed, so a resumed run continues the augmentation stream.
-        self.augment = None
-        section = cfg.get("augment") or {}
-        if section.get("enabled", False):
-            self.augment = DeviceAugment(
-                32, pad=section.get("pad", 4), flip=section.get("flip", 0.5),
-                mean=tuple(section.get("mean", (0., 0., 0.))),
-                std=tuple(section.get("std", (1., 1., 1.))),
-                seed=cfg.seed, device=self.device)
+        self.augment = make_augment(cfg.get("augment") or {}, cfg.seed,
+                                    self.device)
+        if self.augment is not None:
             self.register_stateful("augment")
+            if isinstance(self.augment, DeviceResizedCrop):
+                # the run's log names the recipe that was actually selected
+                self.logger.info("on-device ingest: %r", self.augment)
 
     def get_formatter(self, stage_name):
         return Formatter({"acc": ".1%", "loss": ".5f", "lr": ".2e",

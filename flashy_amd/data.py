@@ -16,9 +16,13 @@ travel as the uint8 NHWC bytes a decoder produces (a quarter of the fp32
 bytes), and one gfx950 kernel crops, flips and normalizes them into the bf16
 NHWC tensor the native models take — with the random draw keyed on a device
 step counter, so it also varies under HIP-graph replay.
+:class:`DeviceResizedCrop` is its ImageNet counterpart: random resized crop
+(scale / aspect), flip and normalize as an integer draw plus a fixed-point
+bilinear resample, under the same counter, mirror and output contracts.
 """
 from __future__ import annotations
 
+import math
 import struct
 import typing as tp
 
@@ -315,3 +319,313 @@ class DeviceAugment:
         scale = torch.tensor(self.scale, dtype=torch.float64)
         bias = torch.tensor(self.bias, dtype=torch.float64)
         return (px.double() * scale + bias).float().bfloat16()
+
+
+_TABLE = 1024      # quantization levels of the area and of the log-ratio draw
+_TRIES = 10        # torchvision's number of attempts before the fallback
+_MAX_SIDE = 32767  # (side << 16) must fit the kernel's int32 coordinates
+
+
+class DeviceResizedCrop:
+    """Random resized crop, horizontal flip and per-channel normalization of
+    a uint8 NHWC batch, as two gfx950 kernels (draw + bilinear resample).
+
+    ``aug(src_u8)`` maps uint8 ``[N, H, W, 3]`` (one size per batch) to bf16
+    ``[N, OH, OW, 3]``.  Train mode is torchvision's
+    ``RandomResizedCrop(out_size, scale, ratio, antialias=False)``,
+    ``RandomHorizontalFlip(flip)`` and ``Normalize(mean, std)``; eval mode
+    (``train=False``) is the centred box of aspect ``OW:OH`` covering
+    ``eval_crop`` of the largest such box, resampled to ``out_size`` without
+    flip — ``eval_crop = 224 / 256`` is ``Resize(256)`` + ``CenterCrop(224)``
+    on a square source.
+
+    The draw follows torchvision's algorithm — ten tries of (area uniform
+    in ``scale``, ratio log-uniform in ``ratio``, uniform position), then
+    the centred fallback box at the violated ratio bound — with one
+    difference: area and ratio are each quantized to 1024 levels, the
+    midpoints of 1024 equal bins, whose square roots the host tabulates in
+    Q16 at construction.  Everything on the device is then integer
+    arithmetic (no ``exp`` / ``log`` / ``sqrt``, whose last bit differs
+    from the host's), so :meth:`boxes_at` reproduces every box bit for bit.
+
+    Resampling is bilinear with half-pixel centres (``align_corners=False``)
+    in fixed point: Q16 source coordinates, 8-bit weights, an exact integer
+    accumulator.  There is NO antialiasing: the source is expected within
+    about 2x of the output size, i.e. pre-resized storage.
+
+    As in :class:`DeviceAugment`, a sample's box is a hash of ``(seed,
+    step, sample index)`` with ``step`` a device int64 counter that a
+    one-thread kernel advances after the resample; all launches are
+    capturable, a replayed HIP graph crops differently every step, and
+    :meth:`state_dict` saves the counter.  The first two hash levels are
+    those of :class:`DeviceAugment`, so one ``seed`` drives both.
+
+    On a CPU device the same arithmetic runs in torch (the test oracle);
+    on CUDA the native extension is required.
+    """
+
+    def __init__(self, out_size: tp.Union[int, tp.Tuple[int, int]],
+                 scale: tp.Sequence[float] = (0.08, 1.0),
+                 ratio: tp.Sequence[float] = (3 / 4, 4 / 3),
+                 flip: float = 0.5,
+                 mean: tp.Sequence[float] = (0., 0., 0.),
+                 std: tp.Sequence[float] = (1., 1., 1.),
+                 eval_crop: float = 0.875, seed: int = 0,
+                 device: tp.Union[torch.device, str] = "cuda"):
+        if isinstance(out_size, int):
+            out_size = (out_size, out_size)
+        self.out_size = (int(out_size[0]), int(out_size[1]))
+        if len(out_size) != 2 or min(self.out_size) < 1:
+            raise ValueError(f"out_size must be positive (OH, OW), got {out_size}")
+        if len(scale) != 2 or not 0.0 < scale[0] <= scale[1] <= 1.0:
+            raise ValueError(
+                f"scale must satisfy 0 < s0 <= s1 <= 1, got {tuple(scale)}")
+        if len(ratio) != 2 or not 0.0 < ratio[0] <= ratio[1] \
+                or not 2.0 ** -14 <= ratio[0] or not ratio[1] <= 2.0 ** 14:
+            raise ValueError(
+                f"ratio must satisfy 0 < r0 <= r1 (within 2^-14 .. 2^14), "
+                f"got {tuple(ratio)}")
+        if not 0.0 <= flip <= 1.0:
+            raise ValueError(f"flip must be a probability, got {flip}")
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError(f"mean and std take 3 channels, got {mean}, {std}")
+        if any(s <= 0 for s in std):
+            raise ValueError(f"std must be positive, got {std}")
+        if not 0.0 < eval_crop <= 1.0:
+            raise ValueError(f"eval_crop must lie in (0, 1], got {eval_crop}")
+        self.scale_range = (float(scale[0]), float(scale[1]))
+        self.ratio = (float(ratio[0]), float(ratio[1]))
+        self.flip = float(flip)
+        self.mean = tuple(float(m) for m in mean)
+        self.std = tuple(float(s) for s in std)
+        self.eval_crop = float(eval_crop)
+        self.seed = int(seed)
+        self.device = torch.device(device)
+        self.scale = tuple(_fp32(1.0 / (255.0 * s)) for s in self.std)
+        self.bias = tuple(_fp32(-m / s) for m, s in zip(self.mean, self.std))
+        # Q16 tables of the draw and Q16 constants of the fallback / eval box
+        s0, s1 = self.scale_range
+        l0, l1 = math.log(self.ratio[0]), math.log(self.ratio[1])
+        self._sa, self._sr, self._sri = [], [], []
+        for j in range(_TABLE):
+            u = (j + 0.5) / _TABLE
+            r = math.exp(l0 + u * (l1 - l0))
+            self._sa.append(round(65536 * math.sqrt(s0 + u * (s1 - s0))))
+            self._sr.append(round(65536 * math.sqrt(r)))
+            self._sri.append(round(65536 / math.sqrt(r)))
+        self._r0_q16 = round(65536 * self.ratio[0])
+        self._r1_q16 = round(65536 * self.ratio[1])
+        self._eval_q16 = round(65536 * self.eval_crop)
+        self._host_step = 0
+        self._step_dev: tp.Optional[torch.Tensor] = None
+        self._tables_dev: tp.Optional[torch.Tensor] = None
+        self._boxes: tp.Optional[torch.Tensor] = None
+        # device box buffers, one per batch size, never released: a captured
+        # graph keeps writing and reading the address it was captured with
+        self._boxes_dev: tp.Dict[int, torch.Tensor] = {}
+        if self.device.type == "cuda":
+            ops.require()
+            self._step_dev = torch.zeros(1, dtype=torch.int64,
+                                         device=self.device)
+            self._tables_dev = torch.tensor(
+                [self._sa, self._sr, self._sri], dtype=torch.int32,
+                device=self.device)
+
+    def __repr__(self) -> str:
+        return (f"DeviceResizedCrop(out_size={self.out_size}, "
+                f"scale={self.scale_range}, ratio={self.ratio}, "
+                f"flip={self.flip}, eval_crop={self.eval_crop}, "
+                f"seed={self.seed}, device={self.device})")
+
+    # -- the draw -----------------------------------------------------------
+    def _in_size(self, in_size: tp.Tuple[int, int]) -> tp.Tuple[int, int]:
+        H, W = int(in_size[0]), int(in_size[1])
+        if min(H, W) < 1 or max(H, W) > _MAX_SIDE:
+            raise ValueError(
+                f"source sides must lie in 1..{_MAX_SIDE}, got {(H, W)}")
+        return H, W
+
+    def _consts(self) -> tp.Tuple[int, int, int, int]:
+        """(flip threshold, r0, r1, eval_crop), the last three in Q16."""
+        return (round(self.flip * (1 << 24)), self._r0_q16, self._r1_q16,
+                self._eval_q16)
+
+    def _rows_at(self, step: int, n: int, in_size: tp.Tuple[int, int],
+                 train: bool = True) -> tp.List[tp.List[int]]:
+        """The ``[n][8]`` rows ``(y0, x0, h, w, flip, step_y, step_x,
+        fallback)`` that ``k_resized_crop_draw`` writes, on Python integers."""
+        H, W = self._in_size(in_size)
+        OH, OW = self.out_size
+        rows = []
+        if not train:
+            if W * OH >= H * OW:        # source at least as wide as the output
+                bh, bw = H << 16, ((H * OW) << 16) // OH
+            else:
+                bh, bw = ((W * OH) << 16) // OW, W << 16
+            h = min(max((bh * self._eval_q16 + (1 << 31)) >> 32, 1), H)
+            w = min(max((bw * self._eval_q16 + (1 << 31)) >> 32, 1), W)
+            row = [(H - h) // 2, (W - w) // 2, h, w, 0,
+                   (h << 16) // OH, (w << 16) // OW, 0]
+            return [list(row) for _ in range(n)]
+        thresh = round(self.flip * (1 << 24))
+        root = math.isqrt((H * W) << 32)
+        key = _mix((self.seed + _GOLDEN * (step + 1)) & _M64)
+        for i in range(n):
+            h0 = _mix((key + _GOLDEN * (i + 1)) & _M64)
+            box = None
+            for t in range(_TRIES):
+                a = _mix((h0 + _GOLDEN * (2 * t + 1)) & _M64)
+                b = _mix((h0 + _GOLDEN * (2 * t + 2)) & _M64)
+                ja = ((a & 0xffffffff) * _TABLE) >> 32
+                jr = ((a >> 32) * _TABLE) >> 32
+                side = (root * self._sa[ja]) >> 16
+                w = (side * self._sr[jr] + (1 << 31)) >> 32
+                h = (side * self._sri[jr] + (1 << 31)) >> 32
+                if 1 <= w <= W and 1 <= h <= H:
+                    box = [((b & 0xffffffff) * (H - h + 1)) >> 32,
+                           ((b >> 32) * (W - w + 1)) >> 32, h, w, 0]
+                    break
+            if box is None:
+                h, w = H, W
+                if (W << 16) < self._r0_q16 * H:       # narrower than r0
+                    h = ((W << 17) + self._r0_q16) // (2 * self._r0_q16)
+                elif (W << 16) > self._r1_q16 * H:     # wider than r1
+                    w = (H * self._r1_q16 + (1 << 15)) >> 16
+                h, w = min(max(h, 1), H), min(max(w, 1), W)
+                box = [(H - h) // 2, (W - w) // 2, h, w, 1]
+            y0, x0, h, w, fallback = box
+            flip = int((_mix((h0 + _GOLDEN * 21) & _M64) >> 40) < thresh)
+            rows.append([y0, x0, h, w, flip, (h << 16) // OH,
+                         (w << 16) // OW, fallback])
+        return rows
+
+    def boxes_at(self, step: int, n: int, in_size: tp.Tuple[int, int]
+                 ) -> tp.Tuple[torch.Tensor, torch.Tensor]:
+        """Host mirror of the kernel's train-mode draw at counter value
+        ``step`` for samples ``0..n-1`` of an ``in_size = (H, W)`` source:
+        CPU tensors ``(int64 [n, 5] of (y0, x0, h, w, flip), bool [n]
+        fallback)``; ``fallback`` marks boxes that came from the centred
+        fallback after ten rejected tries."""
+        rows = torch.tensor(self._rows_at(step, n, in_size),
+                            dtype=torch.int64).view(n, 8)
+        return rows[:, :5].contiguous(), rows[:, 7] != 0
+
+    @property
+    def last_boxes(self) -> tp.Optional[torch.Tensor]:
+        """int32 ``[N, 8]`` rows ``(y0, x0, h, w, flip, step_y, step_x,
+        fallback)`` of the latest call, on this augment's device; reading
+        the attribute does not synchronize.  ``None`` before the first call.
+
+        On CUDA the object keeps one such buffer per batch size for its
+        whole life, so the address a captured graph was recorded with stays
+        valid when other batch sizes come in between: a replay rewrites the
+        buffer of the batch size it was captured at (the tensor this
+        attribute returned after the captured call), and ``last_boxes``
+        keeps naming the buffer of the latest *call*."""
+        return self._boxes
+
+    # -- state --------------------------------------------------------------
+    @property
+    def step(self) -> int:
+        """Number of train-mode batches drawn so far (reads the device)."""
+        if self._step_dev is not None:
+            return int(self._step_dev.item())
+        return self._host_step
+
+    def state_dict(self) -> tp.Dict[str, int]:
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, state: tp.Mapping[str, int]) -> None:
+        self.seed = int(state["seed"])
+        self._host_step = int(state["step"])
+        if self._step_dev is not None:
+            # in place: a captured graph keeps reading this address
+            self._step_dev.fill_(self._host_step)
+
+    # -- the op -------------------------------------------------------------
+    def _check(self, src: torch.Tensor, out: tp.Optional[torch.Tensor]):
+        if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
+            raise TypeError(
+                f"source must be a uint8 tensor, got "
+                f"{getattr(src, 'dtype', type(src))}")
+        if src.dim() != 4 or src.shape[-1] != 3:
+            raise ValueError(
+                f"source must be NHWC [N, H, W, 3], got {tuple(src.shape)}")
+        if not src.is_contiguous():
+            raise ValueError(
+                f"source must be contiguous NHWC, got shape "
+                f"{tuple(src.shape)} with strides {src.stride()}")
+        if src.device.type != self.device.type:
+            raise ValueError(
+                f"source is on {src.device}, this augment on {self.device}")
+        self._in_size((src.shape[1], src.shape[2]))
+        shape = (src.shape[0], *self.out_size, 3)
+        if out is not None:
+            if out.dtype != torch.bfloat16:
+                raise TypeError(f"out must be bfloat16, got {out.dtype}")
+            if tuple(out.shape) != shape or not out.is_contiguous() \
+                    or out.device != src.device:
+                raise ValueError(
+                    f"out must be contiguous {shape} on {src.device}, got "
+                    f"{tuple(out.shape)} on {out.device}")
+        return shape
+
+    def __call__(self, src: torch.Tensor,
+                 out: tp.Optional[torch.Tensor] = None,
+                 train: bool = True) -> torch.Tensor:
+        shape = self._check(src, out)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.bfloat16, device=src.device)
+        N = shape[0]
+        if self._step_dev is not None:
+            boxes = self._boxes_dev.get(N)
+            if boxes is None:
+                boxes = torch.zeros(N, 8, dtype=torch.int32,
+                                    device=src.device)
+                self._boxes_dev[N] = boxes
+            self._boxes = boxes
+            ops.resized_crop(src, out, self._boxes, self._tables_dev,
+                             self._step_dev, self.seed, self._consts(),
+                             self.scale, self.bias, train)
+            return out
+        rows = torch.tensor(
+            self._rows_at(self._host_step, N, src.shape[1:3], train),
+            dtype=torch.int64).view(N, 8)
+        self._boxes = rows.to(torch.int32)
+        out.copy_(self._resample(src, rows))
+        if train:
+            self._host_step += 1
+        return out
+
+    def _resample(self, src: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+        """Torch path of ``k_resized_crop`` on int64 tensors: the exact
+        integer accumulator, then
+        ``(acc.double() * (scale * 2^-16) + bias).float().bfloat16()``."""
+        N = src.shape[0]
+        OH, OW = self.out_size
+        y0, x0, h, w, flip, sy, sx = (rows[:, k:k + 1] for k in range(7))
+
+        def axis(o, lo, size, step):
+            p = (lo << 16) + o * step + (step >> 1) - 32768
+            p = torch.minimum(torch.maximum(p, lo << 16),
+                              (lo + size - 1) << 16)
+            i = p >> 16
+            return i, torch.minimum(i + 1, lo + size - 1), (p >> 8) & 255
+
+        iy, iy1, fy = axis(torch.arange(OH)[None, :], y0, h, sy)    # [N, OH]
+        ox = torch.arange(OW).expand(N, OW)
+        ox = torch.where(flip != 0, OW - 1 - ox, ox)
+        ix, ix1, fx = axis(ox, x0, w, sx)                           # [N, OW]
+        px = src.to(torch.int64)
+        idx_n = torch.arange(N)[:, None, None]
+
+        def at(yy, xx):
+            return px[idx_n, yy[:, :, None], xx[:, None, :]]     # [N,OH,OW,3]
+
+        fy = fy[:, :, None, None]
+        fx = fx[:, None, :, None]
+        acc = ((256 - fy) * ((256 - fx) * at(iy, ix) + fx * at(iy, ix1))
+               + fy * ((256 - fx) * at(iy1, ix) + fx * at(iy1, ix1)))
+        scale = torch.tensor(self.scale, dtype=torch.float64) / 65536.0
+        bias = torch.tensor(self.bias, dtype=torch.float64)
+        return (acc.double() * scale + bias).float().bfloat16()

@@ -15,6 +15,7 @@ flashy_amd/functional.py).
 from __future__ import annotations
 
 import importlib.util
+import math
 import os
 import typing as tp
 from pathlib import Path
@@ -229,6 +230,59 @@ def image_ingest(src: torch.Tensor, out: torch.Tensor,
                      pad, seed & (2 ** 64 - 1), round(p_flip * 2 ** 24),
                      [float(s) for s in scale], [float(b) for b in bias],
                      fill, train, _stream())
+    if train:
+        ext.adam_step_inc(step_dev.data_ptr(), _stream())
+
+
+def resized_crop(src: torch.Tensor, out: torch.Tensor, boxes: torch.Tensor,
+                 tables: torch.Tensor, step_dev: tp.Optional[torch.Tensor],
+                 seed: int, consts: tp.Sequence[int],
+                 scale: tp.Sequence[float], bias: tp.Sequence[float],
+                 train: bool = True) -> None:
+    """Random resized crop / horizontal flip / normalize: uint8 NHWC ``src``
+    [N, H, W, 3] -> bf16 NHWC ``out`` [N, OH, OW, 3], as two launches.
+
+    ``k_resized_crop_draw`` writes each sample's row ``(y0, x0, h, w, flip,
+    step_y, step_x, fallback)`` into ``boxes`` (int32 [N, 8]) and
+    ``k_resized_crop`` resamples the boxes bilinearly.  Train mode hashes
+    (``seed``, ``step_dev``, sample index) and then advances ``step_dev``
+    (int64 device scalar) by one on the same stream; eval mode takes the
+    centred box and neither reads nor advances ``step_dev``.  ``tables`` is
+    the int32 [3, 1024] Q16 block of
+    :class:`flashy_amd.data.DeviceResizedCrop`, ``consts`` its ``(flip
+    threshold, r0, r1, eval_crop)`` integers; ``scale`` / ``bias`` are the
+    per-channel fp32 values of ``u8 * scale + bias``."""
+    ext = require()
+    assert src.dtype == torch.uint8 and out.dtype == torch.bfloat16
+    assert src.is_cuda and out.is_cuda and src.device == out.device
+    assert src.is_contiguous() and out.is_contiguous()
+    assert src.dim() == 4 and out.dim() == 4, (src.shape, out.shape)
+    N, H, W, C = src.shape
+    OH, OW = out.shape[1], out.shape[2]
+    assert C == 3 and out.shape[0] == N and out.shape[3] == 3, \
+        (src.shape, out.shape)
+    assert 1 <= H <= 32767 and 1 <= W <= 32767 and OH >= 1 and OW >= 1, \
+        (src.shape, out.shape)
+    assert boxes.dtype == torch.int32 and tuple(boxes.shape) == (N, 8)
+    assert boxes.is_contiguous() and boxes.device == src.device
+    assert tables.dtype == torch.int32 and tuple(tables.shape) == (3, 1024)
+    assert tables.is_contiguous() and tables.device == src.device
+    assert len(scale) == 3 and len(bias) == 3 and len(consts) == 4
+    thresh, r0, r1, eval_crop = (int(c) for c in consts)
+    assert 0 <= thresh <= 2 ** 24 and 0 < r0 <= r1 < 2 ** 31
+    assert 0 < eval_crop <= 2 ** 16
+    if train:
+        assert step_dev is not None and step_dev.dtype == torch.int64
+        assert step_dev.is_cuda and step_dev.numel() == 1
+    if N:
+        ext.resized_crop_draw(boxes.data_ptr(), tables.data_ptr(),
+                              step_dev.data_ptr() if train else 0, N, H, W,
+                              OH, OW, seed & (2 ** 64 - 1),
+                              math.isqrt((H * W) << 32), thresh, r0, r1,
+                              eval_crop, train, _stream())
+        ext.resized_crop(src.data_ptr(), out.data_ptr(), boxes.data_ptr(), N,
+                         H, W, OH, OW, [float(s) for s in scale],
+                         [float(b) for b in bias], _stream())
     if train:
         ext.adam_step_inc(step_dev.data_ptr(), _stream())
 

@@ -100,6 +100,15 @@ void launch_image_ingest(const void* src, void* out, const void* step_dev,
                          uint64_t seed, uint32_t flip_thresh,
                          const float* scale, const float* bias, int fill,
                          int train, hipStream_t stream);
+void launch_resized_crop_draw(void* boxes, const void* tables,
+                              const void* step_dev, int N, int H, int W,
+                              int OH, int OW, uint64_t seed, uint64_t root_hw,
+                              uint32_t flip_thresh, uint32_t r0, uint32_t r1,
+                              uint32_t eval_crop, int train,
+                              hipStream_t stream);
+void launch_resized_crop(const void* src, void* out, const void* boxes, int N,
+                         int H, int W, int OH, int OW, const float* scale,
+                         const float* bias, hipStream_t stream);
 void launch_maxpool_fwd(const void* x, void* y, void* argmax, ConvDims d,
                         hipStream_t stream);
 void launch_maxpool_bwd(const void* dy, const void* argmax, void* dx,
@@ -431,6 +440,44 @@ PYBIND11_MODULE(_hip_ops, m) {
                                   (const void*)step_dev, N, H, W, OH, OW, pad,
                                   seed, flip_thresh, scale.data(), bias.data(),
                                   fill, train, as_stream(stream));
+              check_last();
+          });
+    // random resized crop (csrc/ingest.hip): the per-sample boxes, int32
+    // [N, 8], then the bilinear resample that reads them
+    m.def("resized_crop_draw",
+          [](uintptr_t boxes, uintptr_t tables, uintptr_t step_dev, int N,
+             int H, int W, int OH, int OW, uint64_t seed, uint64_t root_hw,
+             uint32_t flip_thresh, uint32_t r0, uint32_t r1,
+             uint32_t eval_crop, bool train, uintptr_t stream) {
+              if (train && step_dev == 0)
+                  throw std::invalid_argument("train mode needs step_dev");
+              if (boxes == 0 || boxes % 16 != 0 || tables == 0)
+                  throw std::invalid_argument(
+                      "boxes must be 16-byte aligned, tables non-null");
+              if (N < 1 || OH < 1 || OW < 1 || H < 1 || W < 1 ||
+                  H > 32767 || W > 32767 || r0 == 0 || r1 == 0)
+                  throw std::invalid_argument("resized_crop_draw: bad sizes");
+              launch_resized_crop_draw((void*)boxes, (const void*)tables,
+                                       (const void*)step_dev, N, H, W, OH, OW,
+                                       seed, root_hw, flip_thresh, r0, r1,
+                                       eval_crop, train, as_stream(stream));
+              check_last();
+          });
+    m.def("resized_crop",
+          [](uintptr_t src, uintptr_t out, uintptr_t boxes, int N, int H,
+             int W, int OH, int OW, const std::vector<float>& scale,
+             const std::vector<float>& bias, uintptr_t stream) {
+              if (scale.size() != 3 || bias.size() != 3)
+                  throw std::invalid_argument("scale and bias take 3 values");
+              if (boxes == 0 || boxes % 16 != 0)
+                  throw std::invalid_argument("boxes must be 16-byte aligned");
+              if (N < 1 || OH < 1 || OW < 1 || H < 1 || W < 1 ||
+                  H > 32767 || W > 32767)
+                  throw std::invalid_argument("resized_crop: bad sizes");
+              launch_resized_crop((const void*)src, (void*)out,
+                                  (const void*)boxes, N, H, W, OH, OW,
+                                  scale.data(), bias.data(),
+                                  as_stream(stream));
               check_last();
           });
     m.def("maxpool_fwd",
