@@ -14,7 +14,7 @@ import torch
 from torch.nn import functional as F
 
 from flashy_amd import BaseSolver, Formatter, distrib
-from flashy_amd.data import DeviceAugment, DeviceResizedCrop
+from flashy_amd.data import DeviceAugment, DeviceMix, DeviceResizedCrop
 from flashy_amd.functional import accuracy, cross_entropy
 from flashy_amd.graph import CapturedStep
 from flashy_amd.models.resnet_native import NativeResNet
@@ -69,6 +69,19 @@ def make_augment(section, seed: int, device):
                              **common)
 
 
+def make_mix(section, seed: int, device):
+    """The :class:`DeviceMix` the ``mix`` config section asks for, or None
+    when both alphas are 0 (the default)."""
+    mixup = float(section.get("mixup_alpha", 0.0))
+    cutmix = float(section.get("cutmix_alpha", 0.0))
+    if mixup == 0.0 and cutmix == 0.0:
+        return None
+    return DeviceMix(mixup_alpha=mixup, cutmix_alpha=cutmix,
+                     prob=section.get("prob", 1.0),
+                     switch_prob=section.get("switch_prob", 0.5),
+                     seed=seed, device=device)
+
+
 class Solver(BaseSolver):
     def __init__(self, cfg, model, loaders, optim):
         super().__init__()
@@ -96,6 +109,20 @@ class Solver(BaseSolver):
             if isinstance(self.augment, DeviceResizedCrop):
                 # the run's log names the recipe that was actually selected
                 self.logger.info("on-device ingest: %r", self.augment)
+        # optional label smoothing and Mixup / CutMix of the ingested batch
+        # (train only); the mixer's counter is checkpointed like the augment's
+        self.label_smoothing = float(cfg.get("label_smoothing", 0.0))
+        self.mix = make_mix(cfg.get("mix") or {}, cfg.seed, self.device)
+        if self.mix is not None:
+            if self.augment is None or (self.device.type == "cuda"
+                                        and not self.native):
+                raise ValueError(
+                    "mix.mixup_alpha / mix.cutmix_alpha need "
+                    "augment.enabled=true and, on a GPU, native=true: the "
+                    "mixer works on the bf16 NHWC batch the on-device ingest "
+                    "produces")
+            self.register_stateful("mix")
+            self.logger.info("batch mixing: %r", self.mix)
 
     def get_formatter(self, stage_name):
         return Formatter({"acc": ".1%", "loss": ".5f", "lr": ".2e",
@@ -109,6 +136,14 @@ class Solver(BaseSolver):
         if not self.native:
             x = x.permute(0, 3, 1, 2).float()
         return x
+
+    def _mix(self, x, label):
+        """Mix the ingested batch in place (train only); returns what the
+        loss takes as target.  The torch model's fp32 NCHW input is mixed
+        through its NHWC view."""
+        if self.mix is None:
+            return label
+        return self.mix(x if self.native else x.permute(0, 2, 3, 1), label)
 
     def _capture(self, shape):
         self._static_img = torch.zeros(
@@ -124,17 +159,22 @@ class Solver(BaseSolver):
                 # ingest + counter bump are part of the graph: every replay
                 # reads the advanced counter and crops differently
                 x = self._ingest(x, True)
+            # the mixer draws on the device too; lam reaches the loss
+            # through device memory, so every replay mixes differently
+            target = self._mix(x, self._static_label)
             est = self.model(x)
-            loss = cross_entropy(est, self._static_label)
+            loss = cross_entropy(est, target,
+                                 label_smoothing=self.label_smoothing)
             loss.backward()
             self.optim.step()
             return loss, est
 
-        drawn = self.augment.state_dict() if self.augment is not None else None
+        drawers = [d for d in (self.augment, self.mix) if d is not None]
+        drawn = [d.state_dict() for d in drawers]
         self._graph = CapturedStep(step, warmup=3).capture()
-        if drawn is not None:
+        for drawer, state in zip(drawers, drawn):
             # the warmup steps ran on the zero buffer: give their draws back
-            self.augment.load_state_dict(drawn)
+            drawer.load_state_dict(state)
 
     def _graphed_step(self, img, label):
         """One training step as a single hipGraph replay (static buffers)."""
@@ -154,12 +194,21 @@ class Solver(BaseSolver):
         label = label.to(self.device, non_blocking=True)
         if self.augment is not None:
             img = self._ingest(img, train)
+        target = self._mix(img, label) if train else label
         with torch.autocast("cuda", torch.bfloat16, enabled=self.autocast):
             est = self.model(img)
         if self.native and train:
-            loss = cross_entropy(est, label)  # fused fwd+grad kernel
+            # fused fwd+grad kernel
+            loss = cross_entropy(est, target,
+                                 label_smoothing=self.label_smoothing)
+        elif train and self.mix is not None:
+            loss = cross_entropy(est, target,        # CPU: the torch formula
+                                 label_smoothing=self.label_smoothing)
+        elif train:
+            loss = F.cross_entropy(est, label,
+                                   label_smoothing=self.label_smoothing)
         else:
-            loss = F.cross_entropy(est, label)
+            loss = F.cross_entropy(est, label)       # valid: plain CE
         acc = accuracy(est, label)
         if train:
             self.optim.zero_grad()

@@ -19,13 +19,18 @@ step counter, so it also varies under HIP-graph replay.
 :class:`DeviceResizedCrop` is its ImageNet counterpart: random resized crop
 (scale / aspect), flip and normalize as an integer draw plus a fixed-point
 bilinear resample, under the same counter, mirror and output contracts.
+:class:`DeviceMix` then mixes the ingested batch in place — Mixup / CutMix,
+drawn from the same kind of counter — and hands the loss a
+:class:`MixedTarget` whose ``lam`` lives in device memory.
 """
 from __future__ import annotations
 
+import functools
 import math
 import struct
 import typing as tp
 
+import numpy as np
 import torch
 
 from . import ops
@@ -125,7 +130,7 @@ _GOLDEN = 0x9E3779B97F4A7C15
 
 
 def _mix(z: int) -> int:
-    """splitmix64 finalizer on Python integers (mirrors csrc/ingest.hip)."""
+    """splitmix64 finalizer on Python integers (mirrors csrc/common.h)."""
     z ^= z >> 30
     z = (z * 0xBF58476D1CE4E5B9) & _M64
     z ^= z >> 27
@@ -629,3 +634,291 @@ class DeviceResizedCrop:
         scale = torch.tensor(self.scale, dtype=torch.float64) / 65536.0
         bias = torch.tensor(self.bias, dtype=torch.float64)
         return (acc.double() * scale + bias).float().bfloat16()
+
+
+# ---------------------------------------------------------------------------
+# batch mixing: Mixup / CutMix
+# ---------------------------------------------------------------------------
+
+def _betainc_sym(a: float, x: np.ndarray) -> np.ndarray:
+    """Regularized incomplete beta ``I_x(a, a)`` for ``0 < x <= 0.5`` in
+    double: the continued fraction (modified Lentz), which converges fast
+    there because ``x <= (a + 1) / (2a + 2)``."""
+    tiny = 1e-300
+    c = np.ones_like(x)
+    d = 1.0 - 2.0 * a * x / (a + 1.0)
+    d = 1.0 / np.where(np.abs(d) < tiny, tiny, d)
+    h = d.copy()
+    for m in range(1, 400):
+        m2 = 2 * m
+        for num in (m * (a - m) * x / ((a + m2 - 1.0) * (a + m2)),
+                    -(a + m) * (2.0 * a + m) * x
+                    / ((a + m2) * (a + m2 + 1.0))):
+            d = 1.0 + num * d
+            d = 1.0 / np.where(np.abs(d) < tiny, tiny, d)
+            c = 1.0 + num / c
+            c = np.where(np.abs(c) < tiny, tiny, c)
+            delta = d * c
+            h = h * delta
+        if float(np.max(np.abs(delta - 1.0))) < 1e-16:
+            break
+    front = np.exp(math.lgamma(2.0 * a) - 2.0 * math.lgamma(a)
+                   + a * (np.log(x) + np.log1p(-x)))
+    return front * h / a
+
+
+@functools.lru_cache(maxsize=32)
+def _beta_quantiles(alpha: float, levels: int) -> np.ndarray:
+    half = levels // 2
+    u = (np.arange(half, dtype=np.float64) + 0.5) / levels
+    lo = np.full(half, math.log(1e-300))
+    hi = np.full(half, math.log(0.5))
+    for _ in range(64):
+        mid = 0.5 * (lo + hi)
+        below = _betainc_sym(alpha, np.exp(mid)) < u
+        lo = np.where(below, mid, lo)
+        hi = np.where(below, hi, mid)
+    q = np.exp(0.5 * (lo + hi))
+    q = np.concatenate([q, 1.0 - q[::-1]])
+    q.setflags(write=False)
+    return q
+
+
+def beta_quantiles(alpha: float, levels: int = _TABLE) -> np.ndarray:
+    """The quantiles of Beta(alpha, alpha) at ``(j + 0.5) / levels``, in
+    double: the midpoints of ``levels`` equal-probability bins.  The lower
+    half comes from a bisection (on ``log x``, so tiny quantiles keep their
+    relative precision) over the continued fraction of the regularized
+    incomplete beta; the upper half is its mirror ``q[levels-1-j] = 1 -
+    q[j]``.  math / numpy only; about half a second per new ``alpha``, cached."""
+    if not alpha > 0 or levels < 2 or levels % 2:
+        raise ValueError(f"need alpha > 0 and an even number of levels, got "
+                         f"{alpha}, {levels}")
+    return _beta_quantiles(float(alpha), int(levels)).copy()
+
+
+class MixedTarget(tp.NamedTuple):
+    """What :class:`DeviceMix` returns in place of the labels: sample ``i``
+    is ``lam`` parts class ``target_a[i]`` and ``1 - lam`` parts class
+    ``target_b[i]``.  ``lam`` is a 0-dim fp32 view into the mixer's row
+    buffer, so it follows every later draw (and every graph replay);
+    :func:`flashy_amd.functional.cross_entropy` takes the tuple as target."""
+    target_a: torch.Tensor
+    target_b: torch.Tensor
+    lam: torch.Tensor
+
+
+class DeviceMix:
+    """Mixup and CutMix of a bf16 NHWC batch in place, as two gfx950 kernels
+    (draw + mix), for the whole batch at once.
+
+    ``mixer(x, target)`` mixes sample ``i`` of ``x`` ``[N, H, W, C]`` with
+    sample ``N-1-i`` and returns :class:`MixedTarget` ``(target,
+    target.flip(0), lam)``.  It is timm's ``Mixup`` in batch mode: with
+    probability ``prob`` the batch is mixed; CutMix is chosen with
+    probability ``switch_prob`` when both alphas are positive (else the one
+    enabled mode); ``lam ~ Beta(alpha, alpha)``; Mixup blends ``lam * x +
+    (1 - lam) * x.flip(0)``, CutMix swaps timm's ``rand_bbox`` box and
+    corrects ``lam`` to the box's actual area share.  One difference, in the
+    manner of :class:`DeviceResizedCrop`: Beta is quantized to the midpoints
+    of 1024 equal-probability bins (:func:`beta_quantiles`), tabulated here
+    as fp32 ``lam`` for Mixup and Q16 ``sqrt(1 - lam)`` for CutMix, so the
+    device draw is integer arithmetic plus one double division and
+    :meth:`row_at` reproduces it bit for bit.
+
+    The draw hashes ``(seed, step)`` with ``step`` a device int64 counter
+    that a one-thread kernel advances after the mix; all launches are
+    capturable, so a replayed HIP graph mixes differently every step, and
+    :meth:`state_dict` saves the counter.  The row ``(mode, y0, y1, x0, x1,
+    lam as fp32 bits, j, 0)`` (mode 0 none, 1 mixup, 2 cutmix) lives in ONE
+    persistent int32 ``[8]`` buffer, :attr:`last_row`; the loss kernel reads
+    ``lam`` from it.  The level-one hash key is the augments', the mixer
+    uses its batch-level slot, so one ``seed`` can drive an augment and a
+    mixer without correlated draws.
+
+    On a CPU device the same arithmetic runs in torch (the test oracle,
+    for any float dtype); on CUDA the native extension is required and
+    ``x`` must be bf16, contiguous, 4-D, ``target`` int64 ``[N]``.
+    """
+
+    def __init__(self, mixup_alpha: float = 0., cutmix_alpha: float = 0.,
+                 prob: float = 1., switch_prob: float = 0.5, seed: int = 0,
+                 device: tp.Union[torch.device, str] = "cuda"):
+        if not mixup_alpha >= 0 or not cutmix_alpha >= 0 \
+                or not math.isfinite(mixup_alpha + cutmix_alpha):
+            raise ValueError(f"alphas must be non-negative, got "
+                             f"{mixup_alpha}, {cutmix_alpha}")
+        if mixup_alpha == 0 and cutmix_alpha == 0:
+            raise ValueError("at least one of mixup_alpha, cutmix_alpha must "
+                             "be positive")
+        if not 0.0 <= prob <= 1.0:
+            raise ValueError(f"prob must be a probability, got {prob}")
+        if not 0.0 <= switch_prob <= 1.0:
+            raise ValueError(
+                f"switch_prob must be a probability, got {switch_prob}")
+        self.mixup_alpha = float(mixup_alpha)
+        self.cutmix_alpha = float(cutmix_alpha)
+        self.prob = float(prob)
+        self.switch_prob = float(switch_prob)
+        self.seed = int(seed)
+        self.device = torch.device(device)
+        # the two tables; None for a disabled mode
+        self.lam_table: tp.Optional[np.ndarray] = None      # fp32 [1024]
+        self.sq_table: tp.Optional[np.ndarray] = None       # int32 [1024]
+        if self.mixup_alpha > 0:
+            self.lam_table = beta_quantiles(self.mixup_alpha).astype(
+                np.float32)
+        if self.cutmix_alpha > 0:
+            self.sq_table = np.rint(65536.0 * np.sqrt(
+                1.0 - beta_quantiles(self.cutmix_alpha))).astype(np.int32)
+        self._host_step = 0
+        self._step_dev: tp.Optional[torch.Tensor] = None
+        self._lam_dev: tp.Optional[torch.Tensor] = None
+        self._sq_dev: tp.Optional[torch.Tensor] = None
+        # ONE row buffer for the object's life: a captured graph and every
+        # MixedTarget.lam handed out keep reading this address
+        self._row = torch.zeros(8, dtype=torch.int32, device=self.device)
+        self._row[5:6].view(torch.float32).fill_(1.0)
+        self._lam = self._row[5:6].view(torch.float32)[0]
+        if self.device.type == "cuda":
+            ops.require()
+            self._step_dev = torch.zeros(1, dtype=torch.int64,
+                                         device=self.device)
+            if self.lam_table is not None:
+                self._lam_dev = torch.from_numpy(self.lam_table).to(
+                    self.device)
+            if self.sq_table is not None:
+                self._sq_dev = torch.from_numpy(self.sq_table).to(self.device)
+
+    def __repr__(self) -> str:
+        return (f"DeviceMix(mixup_alpha={self.mixup_alpha}, "
+                f"cutmix_alpha={self.cutmix_alpha}, prob={self.prob}, "
+                f"switch_prob={self.switch_prob}, seed={self.seed}, "
+                f"device={self.device})")
+
+    # -- the draw -----------------------------------------------------------
+    def _in_size(self, in_size: tp.Tuple[int, int]) -> tp.Tuple[int, int]:
+        H, W = int(in_size[0]), int(in_size[1])
+        if min(H, W) < 1 or max(H, W) > _MAX_SIDE:
+            raise ValueError(
+                f"image sides must lie in 1..{_MAX_SIDE}, got {(H, W)}")
+        return H, W
+
+    def row_at(self, step: int, in_size: tp.Tuple[int, int]) -> tp.List[int]:
+        """Host mirror of ``k_batch_mix_draw`` at counter value ``step`` for
+        ``in_size = (H, W)`` images: the 8 integers ``(mode, y0, y1, x0, x1,
+        lam as fp32 bits, j, 0)``."""
+        H, W = self._in_size(in_size)
+        key = _mix((self.seed + _GOLDEN * (step + 1)) & _M64)
+        hm = _mix(key)
+        a = _mix((hm + _GOLDEN) & _M64)
+        b = _mix((hm + 2 * _GOLDEN) & _M64)
+        c = _mix((hm + 3 * _GOLDEN) & _M64)
+        apply = (a >> 40) < round(self.prob * (1 << 24))
+        cut = self.sq_table is not None and (
+            self.lam_table is None
+            or (a & 0xffffff) < round(self.switch_prob * (1 << 24)))
+        j = ((b & 0xffffffff) * _TABLE) >> 32
+        mode, y0, y1, x0, x1, lam = 0, 0, 0, 0, 0, 1.0
+        if apply and not cut:
+            mode, lam = 1, float(self.lam_table[j])
+        elif apply:
+            mode = 2
+            sq = int(self.sq_table[j])
+            cut_h, cut_w = (H * sq) >> 16, (W * sq) >> 16
+            cy = ((c & 0xffffffff) * H) >> 32
+            cx = ((c >> 32) * W) >> 32
+            y0, y1 = max(cy - cut_h // 2, 0), min(cy + cut_h // 2, H)
+            x0, x1 = max(cx - cut_w // 2, 0), min(cx + cut_w // 2, W)
+            lam = _fp32(1.0 - ((y1 - y0) * (x1 - x0)) / (H * W))
+        bits = struct.unpack("i", struct.pack("f", lam))[0]
+        return [mode, y0, y1, x0, x1, bits, j, 0]
+
+    @property
+    def last_row(self) -> torch.Tensor:
+        """The int32 ``[8]`` row of the latest call (or replay), on this
+        mixer's device — always the same buffer; reading the attribute does
+        not synchronize."""
+        return self._row
+
+    # -- state --------------------------------------------------------------
+    @property
+    def step(self) -> int:
+        """Number of batches drawn so far (reads the device)."""
+        if self._step_dev is not None:
+            return int(self._step_dev.item())
+        return self._host_step
+
+    def state_dict(self) -> tp.Dict[str, int]:
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, state: tp.Mapping[str, int]) -> None:
+        self.seed = int(state["seed"])
+        self._host_step = int(state["step"])
+        if self._step_dev is not None:
+            # in place: a captured graph keeps reading this address
+            self._step_dev.fill_(self._host_step)
+
+    # -- the op -------------------------------------------------------------
+    def _check(self, x: torch.Tensor, target: torch.Tensor) -> None:
+        if not isinstance(x, torch.Tensor) or not x.is_floating_point():
+            raise TypeError(f"x must be a float tensor, got "
+                            f"{getattr(x, 'dtype', type(x))}")
+        if x.dim() != 4:
+            raise ValueError(
+                f"x must be NHWC [N, H, W, C], got {tuple(x.shape)}")
+        if x.device.type != self.device.type:
+            raise ValueError(f"x is on {x.device}, this mixer on {self.device}")
+        if self._step_dev is not None:
+            if x.dtype != torch.bfloat16:
+                raise TypeError(f"x must be bfloat16 on CUDA, got {x.dtype}")
+            if not x.is_contiguous():
+                raise ValueError(
+                    f"x must be contiguous NHWC, got shape {tuple(x.shape)} "
+                    f"with strides {x.stride()}")
+        if not isinstance(target, torch.Tensor) \
+                or target.dtype != torch.int64:
+            raise TypeError(f"target must be an int64 tensor, got "
+                            f"{getattr(target, 'dtype', type(target))}")
+        if tuple(target.shape) != (x.shape[0],) \
+                or target.device != x.device:
+            raise ValueError(
+                f"target must be [{x.shape[0]}] on {x.device}, got "
+                f"{tuple(target.shape)} on {target.device}")
+        self._in_size((x.shape[1], x.shape[2]))
+
+    def __call__(self, x: torch.Tensor, target: torch.Tensor) -> MixedTarget:
+        self._check(x, target)
+        mixed = MixedTarget(target, target.flip(0), self._lam)
+        if self._step_dev is not None:
+            ops.batch_mix_draw(self._row, self._lam_dev, self._sq_dev,
+                               self._step_dev, self.seed, x.shape[1:3],
+                               self.prob, self.switch_prob)
+            ops.batch_mix(x, self._row)
+            ops.adam_step_inc(self._step_dev)
+            return mixed
+        row = self.row_at(self._host_step, x.shape[1:3])
+        self._row.copy_(torch.tensor(row, dtype=torch.int32))
+        self._reference(x, row)
+        self._host_step += 1
+        return mixed
+
+    @staticmethod
+    def _reference(x: torch.Tensor, row: tp.Sequence[int]) -> None:
+        """Torch path of ``k_batch_mix``, in place: fp32 products and sum,
+        each rounded on its own, then one rounding to ``x.dtype``; the box
+        is clamped into the image as the kernel clamps it."""
+        mode = int(row[0])
+        H, W = x.shape[1], x.shape[2]
+        if mode == 1:
+            lam = torch.tensor([int(row[5])], dtype=torch.int32).view(
+                torch.float32)[0]
+            oml = 1.0 - lam                             # fp32, as the kernel
+            xf = x.float()
+            x.copy_((xf * lam + xf.flip(0) * oml).to(x.dtype))
+        elif mode == 2:
+            y0 = min(max(int(row[1]), 0), H)
+            y1 = min(max(int(row[2]), y0), H)
+            x0 = min(max(int(row[3]), 0), W)
+            x1 = min(max(int(row[4]), x0), W)
+            x[:, y0:y1, x0:x1] = x[:, y0:y1, x0:x1].flip(0).clone()

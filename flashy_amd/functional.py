@@ -9,9 +9,12 @@ native extension is required.
 """
 from __future__ import annotations
 
+import typing as tp
+
 import torch
 
 from . import ops
+from .data import MixedTarget
 
 
 class _CrossEntropy(torch.autograd.Function):
@@ -31,14 +34,64 @@ class _CrossEntropy(torch.autograd.Function):
         return dlogits * grad_out, None
 
 
-def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+class _CrossEntropyMix(torch.autograd.Function):
+    """Mixed / smoothed target: ``target_b`` and ``lam`` may be None."""
+
+    @staticmethod
+    def forward(ctx, logits, target, target_b, lam, eps: float):
+        B, C = logits.shape
+        dlogits = torch.empty_like(logits)
+        loss = torch.zeros((), dtype=torch.float32, device=logits.device)
+        ops.cross_entropy_mix_fwd_bwd(
+            logits.contiguous(), target.contiguous(),
+            target_b.contiguous() if target_b is not None else None, lam,
+            dlogits, loss, eps, loss_scale=1.0 / B, grad_scale=1.0 / B)
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * grad_out, None, None, None, None
+
+
+def cross_entropy(logits: torch.Tensor,
+                  target: tp.Union[torch.Tensor, MixedTarget],
+                  label_smoothing: float = 0.0) -> torch.Tensor:
     """Mean cross-entropy over [B, C] logits (fp32 or bf16) and int64 targets.
 
-    GPU: one fused kernel producing loss + dlogits.  CPU: torch fallback.
+    ``target`` may also be the :class:`flashy_amd.data.MixedTarget` of a
+    :class:`flashy_amd.data.DeviceMix`; the loss is then ``lam * CE(logits,
+    target_a) + (1 - lam) * CE(logits, target_b)``, with ``lam`` read on the
+    device (so a captured loss follows each replay's draw) and no gradient
+    into ``lam``.  ``label_smoothing`` is torch's: the target distribution
+    becomes ``(1 - eps) * target + eps / C``.
+
+    GPU: one fused kernel producing loss + dlogits (``k_cross_entropy`` for
+    a plain target without smoothing, else ``k_cross_entropy_mix``).  CPU:
+    torch fallback.
     """
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(
+            f"label_smoothing must lie in [0, 1], got {label_smoothing}")
+    mixed = isinstance(target, MixedTarget)
     if logits.device.type != "cuda":
-        return torch.nn.functional.cross_entropy(logits, target)
-    return _CrossEntropy.apply(logits, target)
+        ce = torch.nn.functional.cross_entropy
+        if not mixed:
+            return ce(logits, target, label_smoothing=label_smoothing)
+        lam = target.lam.detach().reshape(())
+        return (lam * ce(logits, target.target_a,
+                         label_smoothing=label_smoothing)
+                + (1 - lam) * ce(logits, target.target_b,
+                                 label_smoothing=label_smoothing))
+    if mixed:
+        return _CrossEntropyMix.apply(logits, target.target_a,
+                                      target.target_b, target.lam,
+                                      float(label_smoothing))
+    if label_smoothing == 0.0:
+        return _CrossEntropy.apply(logits, target)
+    return _CrossEntropyMix.apply(logits, target, None, None,
+                                  float(label_smoothing))
 
 
 class _BCEWithLogits(torch.autograd.Function):

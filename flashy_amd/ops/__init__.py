@@ -287,6 +287,71 @@ def resized_crop(src: torch.Tensor, out: torch.Tensor, boxes: torch.Tensor,
         ext.adam_step_inc(step_dev.data_ptr(), _stream())
 
 
+# ---------------------------------------------------------------------------
+# batch mixing (Mixup / CutMix on bf16 NHWC; see flashy_amd/data.py)
+# ---------------------------------------------------------------------------
+
+# layout of the int32 [8] mix row, see csrc/mix.hip
+MIX_MODE, MIX_Y0, MIX_Y1, MIX_X0, MIX_X1, MIX_LAM, MIX_J = range(7)
+
+
+def _check_mix_row(row: torch.Tensor) -> None:
+    assert row.dtype == torch.int32 and tuple(row.shape) == (8,), \
+        (row.dtype, row.shape)
+    assert row.is_cuda and row.is_contiguous()
+    assert row.data_ptr() % 16 == 0, "the kernels read the row as two int4"
+
+
+def batch_mix_draw(row: torch.Tensor, lam_table: tp.Optional[torch.Tensor],
+                   sq_table: tp.Optional[torch.Tensor],
+                   step_dev: torch.Tensor, seed: int,
+                   in_size: tp.Tuple[int, int], prob: float,
+                   switch_prob: float) -> None:
+    """Write the batch's mix row ``(mode, y0, y1, x0, x1, lam as fp32 bits,
+    j, 0)`` into ``row`` (int32 [8]) from a hash of (``seed``,
+    ``step_dev``); one one-thread launch, ``step_dev`` (int64 device scalar)
+    is read, not advanced.  ``lam_table`` (fp32 [1024]) enables mixup,
+    ``sq_table`` (int32 [1024], Q16) cutmix: the tables of
+    :class:`flashy_amd.data.DeviceMix`; ``in_size`` is the ``(H, W)`` the
+    cutmix box is drawn for."""
+    ext = require()
+    _check_mix_row(row)
+    assert lam_table is not None or sq_table is not None
+    for table, dtype in ((lam_table, torch.float32), (sq_table, torch.int32)):
+        if table is not None:
+            assert table.dtype == dtype and tuple(table.shape) == (1024,)
+            assert table.is_contiguous() and table.device == row.device
+    assert step_dev.dtype == torch.int64 and step_dev.is_cuda
+    assert step_dev.numel() == 1
+    H, W = int(in_size[0]), int(in_size[1])
+    assert 1 <= H <= 32767 and 1 <= W <= 32767, in_size
+    assert 0.0 <= prob <= 1.0 and 0.0 <= switch_prob <= 1.0
+    ext.batch_mix_draw(row.data_ptr(),
+                       lam_table.data_ptr() if lam_table is not None else 0,
+                       sq_table.data_ptr() if sq_table is not None else 0,
+                       step_dev.data_ptr(), H, W, seed & (2 ** 64 - 1),
+                       round(prob * 2 ** 24), round(switch_prob * 2 ** 24),
+                       lam_table is not None, sq_table is not None, _stream())
+
+
+def batch_mix(x: torch.Tensor, row: torch.Tensor) -> None:
+    """Mix the bf16 NHWC batch ``x`` [N, H, W, C] in place, sample ``i``
+    with sample ``N-1-i``, as the int32 [8] device ``row`` says: mode 1
+    blends ``bf16(lam*x_i + (1-lam)*x_p)`` (every fp32 operation rounded on
+    its own), mode 2 swaps the box ``[y0, y1) x [x0, x1)``, any other mode
+    leaves ``x`` alone.  Any row is safe: the kernel clamps the box into the
+    image."""
+    ext = require()
+    _check_mix_row(row)
+    assert x.dtype == torch.bfloat16 and x.is_cuda and x.device == row.device
+    assert x.dim() == 4 and x.is_contiguous(), (x.shape, x.stride())
+    assert x.data_ptr() % 16 == 0, "16-byte vectors need an aligned batch"
+    N, H, W, C = x.shape
+    assert H <= 32767 and W <= 32767, x.shape
+    if x.numel():
+        ext.batch_mix(x.data_ptr(), row.data_ptr(), N, H, W, C, _stream())
+
+
 def maxpool_fwd(x: torch.Tensor, y: torch.Tensor, argmax: torch.Tensor,
                 d: "ConvDims") -> None:
     assert d.C % 8 == 0
@@ -610,6 +675,37 @@ def cross_entropy_fwd_bwd(logits: torch.Tensor, target: torch.Tensor,
     ext.cross_entropy(logits.data_ptr(), target.data_ptr(), dlogits.data_ptr(),
                       loss_sum.data_ptr(), B, C, loss_scale, grad_scale,
                       _is_bf16(logits), _stream())
+
+
+def cross_entropy_mix_fwd_bwd(logits: torch.Tensor, target: torch.Tensor,
+                              target_b: tp.Optional[torch.Tensor],
+                              lam: tp.Optional[torch.Tensor],
+                              dlogits: torch.Tensor, loss_sum: torch.Tensor,
+                              label_smoothing: float, loss_scale: float,
+                              grad_scale: float) -> None:
+    """Cross-entropy against the mixed, smoothed target ``(1-eps) *
+    (lam*onehot(target) + (1-lam)*onehot(target_b)) + eps/C``.  ``target_b``
+    None means ``target``; ``lam`` is a one-element fp32 device tensor the
+    kernel reads (None: 1), so a captured launch follows its value."""
+    ext = require()
+    B, C = logits.shape
+    assert logits.is_contiguous() and logits.is_cuda
+    assert dlogits.is_contiguous() and dlogits.dtype == logits.dtype
+    assert tuple(dlogits.shape) == (B, C)
+    for t in (target, target_b):
+        if t is not None:
+            assert t.dtype == torch.int64 and tuple(t.shape) == (B,)
+            assert t.is_contiguous() and t.device == logits.device
+    if lam is not None:
+        assert lam.dtype == torch.float32 and lam.numel() == 1
+        assert lam.device == logits.device
+    assert 0.0 <= label_smoothing <= 1.0, label_smoothing
+    ext.cross_entropy_mix(logits.data_ptr(), target.data_ptr(),
+                          target_b.data_ptr() if target_b is not None else 0,
+                          lam.data_ptr() if lam is not None else 0,
+                          dlogits.data_ptr(), loss_sum.data_ptr(), B, C,
+                          float(label_smoothing), loss_scale, grad_scale,
+                          _is_bf16(logits), _stream())
 
 
 def bce_logits_fwd_bwd(x: torch.Tensor, dx: torch.Tensor,

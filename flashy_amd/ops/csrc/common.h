@@ -38,6 +38,15 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
     return (uint16_t)(v.u32 >> 16);
 }
 
+// splitmix64 finalizer: the hash behind every on-device draw (ingest.hip,
+// mix.hip); flashy_amd/data.py mirrors it on Python integers (_mix)
+__device__ __forceinline__ unsigned long long ingest_mix(unsigned long long z) {
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+
 // wave-wide reductions over all 64 lanes
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

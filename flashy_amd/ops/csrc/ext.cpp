@@ -109,6 +109,19 @@ void launch_resized_crop_draw(void* boxes, const void* tables,
 void launch_resized_crop(const void* src, void* out, const void* boxes, int N,
                          int H, int W, int OH, int OW, const float* scale,
                          const float* bias, hipStream_t stream);
+void launch_batch_mix_draw(void* row, const void* lam_table,
+                           const void* sq_table, const void* step_dev, int H,
+                           int W, uint64_t seed, uint32_t prob_thresh,
+                           uint32_t switch_thresh, int mixup, int cutmix,
+                           hipStream_t stream);
+void launch_batch_mix(void* x, const void* row, int N, int H, int W, int C,
+                      hipStream_t stream);
+void launch_cross_entropy_mix(const void* logits, const void* target,
+                              const void* target_b, const void* lam,
+                              void* dlogits, void* loss_sum, int64_t B,
+                              int64_t C, float eps, float loss_scale,
+                              float grad_scale, int is_bf16,
+                              hipStream_t stream);
 void launch_maxpool_fwd(const void* x, void* y, void* argmax, ConvDims d,
                         hipStream_t stream);
 void launch_maxpool_bwd(const void* dy, const void* argmax, void* dx,
@@ -480,6 +493,40 @@ PYBIND11_MODULE(_hip_ops, m) {
                                   as_stream(stream));
               check_last();
           });
+    // Mixup / CutMix (csrc/mix.hip): the batch's mix row, int32 [8], then
+    // the in-place blend or box swap that reads it
+    m.def("batch_mix_draw",
+          [](uintptr_t row, uintptr_t lam_table, uintptr_t sq_table,
+             uintptr_t step_dev, int H, int W, uint64_t seed,
+             uint32_t prob_thresh, uint32_t switch_thresh, bool mixup,
+             bool cutmix, uintptr_t stream) {
+              if (row == 0 || row % 16 != 0 || step_dev == 0)
+                  throw std::invalid_argument(
+                      "row must be 16-byte aligned, step_dev non-null");
+              if ((mixup && lam_table == 0) || (cutmix && sq_table == 0))
+                  throw std::invalid_argument(
+                      "an enabled mode needs its table");
+              if (H < 1 || W < 1 || H > 32767 || W > 32767)
+                  throw std::invalid_argument("batch_mix_draw: bad sizes");
+              launch_batch_mix_draw((void*)row, (const void*)lam_table,
+                                    (const void*)sq_table,
+                                    (const void*)step_dev, H, W, seed,
+                                    prob_thresh, switch_thresh, mixup ? 1 : 0,
+                                    cutmix ? 1 : 0, as_stream(stream));
+              check_last();
+          });
+    m.def("batch_mix",
+          [](uintptr_t x, uintptr_t row, int N, int H, int W, int C,
+             uintptr_t stream) {
+              if (x == 0 || x % 16 != 0 || row == 0 || row % 16 != 0)
+                  throw std::invalid_argument(
+                      "x and row must be 16-byte aligned");
+              if (N < 1 || H < 1 || W < 1 || C < 1 || H > 32767 || W > 32767)
+                  throw std::invalid_argument("batch_mix: bad sizes");
+              launch_batch_mix((void*)x, (const void*)row, N, H, W, C,
+                               as_stream(stream));
+              check_last();
+          });
     m.def("maxpool_fwd",
           [](uintptr_t x, uintptr_t y, uintptr_t argmax, int N, int H, int W,
              int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
@@ -508,6 +555,22 @@ PYBIND11_MODULE(_hip_ops, m) {
                                    (void*)dlogits, (void*)loss_sum, B, C,
                                    loss_scale, grad_scale, is_bf16 ? 1 : 0,
                                    as_stream(stream));
+              check_last();
+          });
+
+    // target_b = 0: same as target; lam = 0 (null): 1
+    m.def("cross_entropy_mix",
+          [](uintptr_t logits, uintptr_t target, uintptr_t target_b,
+             uintptr_t lam, uintptr_t dlogits, uintptr_t loss_sum, int64_t B,
+             int64_t C, float eps, float loss_scale, float grad_scale,
+             bool is_bf16, uintptr_t stream) {
+              launch_cross_entropy_mix((const void*)logits,
+                                       (const void*)target,
+                                       (const void*)target_b,
+                                       (const void*)lam, (void*)dlogits,
+                                       (void*)loss_sum, B, C, eps, loss_scale,
+                                       grad_scale, is_bf16 ? 1 : 0,
+                                       as_stream(stream));
               check_last();
           });
 

@@ -34,13 +34,6 @@ struct IngestArgs {
     int fill, train;
 };
 
-__device__ __forceinline__ unsigned long long ingest_mix(unsigned long long z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
 __global__ void __launch_bounds__(256)
 k_image_ingest(IngestArgs a) {
     const unsigned long long G = 0x9E3779B97F4A7C15ull;

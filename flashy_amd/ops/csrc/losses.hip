@@ -95,6 +95,90 @@ extern "C" void launch_cross_entropy(const void* logits, const void* target,
 }
 
 // ---------------------------------------------------------------------------
+// Cross-entropy against a mixed, smoothed target (Mixup / CutMix + label
+// smoothing; flashy_amd.data.DeviceMix).  Per row, with ta = target[row],
+// tb = target_b[row] (null: tb = ta), lam = *lam_ptr (null: 1) and
+//   t = (1-eps) * (lam*onehot(ta) + (1-lam)*onehot(tb)) + eps/C :
+//   loss_row = lse - [(1-eps)*(lam*x[ta] + (1-lam)*x[tb]) + eps*mean(x)]
+//   dlogits  = (softmax - t) * grad_scale
+// which is lam*CE(x, ta, eps) + (1-lam)*CE(x, tb, eps); when ta == tb both
+// one-hot terms land on the same class.  lam is read from device memory, so
+// a captured loss follows the mix row each replay draws.  Same one wave per
+// row shape as k_cross_entropy; the second pass also accumulates sum(x).
+// ---------------------------------------------------------------------------
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_cross_entropy_mix(const T* __restrict__ logits,
+                    const int64_t* __restrict__ target,
+                    const int64_t* __restrict__ target_b,
+                    const float* __restrict__ lam_ptr, T* __restrict__ dlogits,
+                    float* __restrict__ loss_sum, int64_t B, int64_t C,
+                    float eps, float loss_scale, float grad_scale) {
+    const int wave = threadIdx.x / WAVE_SIZE;          // 4 waves per block
+    const int lane = threadIdx.x % WAVE_SIZE;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+    if (row >= B) return;
+    const T* x = logits + row * C;
+    T* dx = dlogits + row * C;
+    const int64_t ta = target[row];
+    const int64_t tb = target_b ? target_b[row] : ta;
+    const float lam = lam_ptr ? *lam_ptr : 1.f;
+    const float wa = (1.f - eps) * lam;                // weight of onehot(ta)
+    const float wb = (1.f - eps) * (1.f - lam);        // weight of onehot(tb)
+    const float uni = eps / (float)C;
+
+    float mx = -INFINITY;
+    for (int64_t c = lane; c < C; c += WAVE_SIZE)
+        mx = fmaxf(mx, load_f32(x, c));
+    mx = wave_bcast(wave_max(mx));
+
+    float sum = 0.f, sx = 0.f;
+    for (int64_t c = lane; c < C; c += WAVE_SIZE) {
+        const float v = load_f32(x, c);
+        sum += expf(v - mx);
+        sx += v;
+    }
+    sum = wave_bcast(wave_sum(sum));
+    sx = wave_sum(sx);                                 // lane 0 only
+    const float inv_sum = 1.f / sum;
+    const float lse = mx + logf(sum);
+
+    for (int64_t c = lane; c < C; c += WAVE_SIZE) {
+        float p = expf(load_f32(x, c) - mx) * inv_sum;
+        float t = uni + (c == ta ? wa : 0.f) + (c == tb ? wb : 0.f);
+        store_f32(dx, c, (p - t) * grad_scale);
+    }
+    if (lane == 0) {
+        // a target outside [0, C) matches no class above; do not read there
+        const float xa = ta >= 0 && ta < C ? load_f32(x, ta) : 0.f;
+        const float xb = tb >= 0 && tb < C ? load_f32(x, tb) : 0.f;
+        float loss = lse - (wa * xa + wb * xb + uni * sx);
+        atomicAdd(loss_sum, loss * loss_scale);
+    }
+}
+
+// target_b and lam may be null (see above)
+extern "C" void launch_cross_entropy_mix(const void* logits, const void* target,
+                                         const void* target_b, const void* lam,
+                                         void* dlogits, void* loss_sum,
+                                         int64_t B, int64_t C, float eps,
+                                         float loss_scale, float grad_scale,
+                                         int is_bf16, hipStream_t stream) {
+    int grid = (int)((B + 3) / 4);
+    if (is_bf16)
+        k_cross_entropy_mix<uint16_t><<<grid, 256, 0, stream>>>(
+            (const uint16_t*)logits, (const int64_t*)target,
+            (const int64_t*)target_b, (const float*)lam, (uint16_t*)dlogits,
+            (float*)loss_sum, B, C, eps, loss_scale, grad_scale);
+    else
+        k_cross_entropy_mix<float><<<grid, 256, 0, stream>>>(
+            (const float*)logits, (const int64_t*)target,
+            (const int64_t*)target_b, (const float*)lam, (float*)dlogits,
+            (float*)loss_sum, B, C, eps, loss_scale, grad_scale);
+}
+
+// ---------------------------------------------------------------------------
 // BCE-with-logits against a CONSTANT target (the GAN convention:
 // flashy_amd/adversarial.py trains towards D(fake)=1 / D(real)=0):
 //   loss_i = max(x,0) - x*t + log1p(exp(-|x|))
