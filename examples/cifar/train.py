@@ -9,7 +9,8 @@ import torch
 import flashy_amd
 from flashy_amd import distrib
 from flashy_amd.models import native_resnet18, resnet18
-from flashy_amd.optim import FusedSGD, MultiStep, WarmupCosine, WarmupLinear
+from flashy_amd.optim import (LARS, FusedSGD, MultiStep, WarmupCosine,
+                              WarmupLinear, no_decay_1d)
 from flashy_amd import xp as fxp
 
 from .solver import Solver, SyntheticCIFAR
@@ -39,6 +40,18 @@ def get_schedule(cfg, steps_per_epoch: int):
                  **warmup)
 
 
+def get_tensor_options(cfg):
+    """``no_decay_1d`` and the ``lars:`` section -> the ``param_options`` /
+    ``lars`` keywords of FusedSGD (both None = off)."""
+    section = cfg.get("lars") or {}
+    lars = None
+    if section.get("enabled", False):
+        lars = LARS(eta=section.get("eta", 1e-3), eps=section.get("eps", 1e-8))
+    return dict(
+        param_options=no_decay_1d if cfg.get("no_decay_1d", False) else None,
+        lars=lars)
+
+
 def get_solver(cfg):
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu") \
         if cfg.device == "auto" else torch.device(cfg.device)
@@ -52,12 +65,16 @@ def get_solver(cfg):
         optim = FusedSGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
                          weight_decay=cfg.weight_decay, bf16_mirror=True,
                          schedule=get_schedule(cfg, len(loaders["train"])),
-                         max_grad_norm=cfg.get("max_grad_norm"))
+                         max_grad_norm=cfg.get("max_grad_norm"),
+                         **get_tensor_options(cfg))
         model.enable_wt_cache()
         return Solver(cfg, model, loaders, optim)
     if (cfg.get("schedule") or {}).get("kind") or cfg.get("max_grad_norm"):
         raise ValueError("schedule / max_grad_norm need the native path "
                          "(FusedSGD); this run uses torch.optim.SGD")
+    if any(v is not None for v in get_tensor_options(cfg).values()):
+        raise ValueError("no_decay_1d / lars need the native path (FusedSGD); "
+                         "this run uses torch.optim.SGD")
     model = resnet18(num_classes=cfg.num_classes, small_input=True).to(device)
     distrib.broadcast_model(model)
     optim = torch.optim.SGD(model.parameters(), lr=cfg.lr,

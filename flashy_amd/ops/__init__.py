@@ -192,6 +192,187 @@ def optim_prepare(hyper: torch.Tensor, schedule: tp.Any, base_lr: float,
 
 
 # ---------------------------------------------------------------------------
+# segmented optimizer path: per-tensor weight decay / lr scale / LARS
+# ---------------------------------------------------------------------------
+
+SEG_CHUNK = 4096
+
+
+def seg_chunks(sizes: tp.Sequence[int], chunk: int = SEG_CHUNK
+               ) -> tp.List[tp.Tuple[int, int, int]]:
+    """Cut a flat arena holding tensors of ``sizes`` (packed back to back)
+    into ``(start, len, tensor)`` chunks: the intersection of each fixed
+    window ``[w * chunk, (w + 1) * chunk)`` with each tensor.  Chunks never
+    cross a tensor boundary, edges inside a tensor are window edges, and
+    there are at most ``ceil(n / chunk) + T - 1`` of them.  Pure host code."""
+    if chunk <= 0 or chunk % 4:
+        raise ValueError(f"chunk must be a positive multiple of 4: {chunk}")
+    out = []
+    offset = 0
+    for t, size in enumerate(sizes):
+        start, end = offset, offset + int(size)
+        while start < end:
+            stop = min(end, (start // chunk + 1) * chunk)
+            out.append((start, stop - start, t))
+            start = stop
+        offset = end
+    return out
+
+
+class SegTable:
+    """Device-resident chunk table and per-tensor hyperparameter arrays of
+    one flat arena (built once on the host, see :func:`seg_chunks`).
+
+    ``chunks`` is int32 ``[C, 4]``: 64-bit ``start``, ``len``, ``tensor`` —
+    one 16-byte entry per chunk.  ``tensor_chunk`` (int32 ``[T + 1]``) maps a
+    tensor to its chunk range; ``wd`` / ``lr_scale`` (fp32) and ``lars_on``
+    (int32) hold one value per tensor.  :meth:`set_options` rewrites the
+    per-tensor values in place, so a captured step sees them on replay."""
+
+    def __init__(self, sizes: tp.Sequence[int], wd: tp.Sequence[float],
+                 lr_scale: tp.Sequence[float], lars_on: tp.Sequence[bool],
+                 device: tp.Any, chunk: int = SEG_CHUNK):
+        self.sizes = [int(s) for s in sizes]
+        self.n = sum(self.sizes)
+        self.n_tensors = len(self.sizes)
+        self.chunk = chunk
+        chunks = seg_chunks(self.sizes, chunk)
+        if not chunks:
+            raise ValueError("empty arena")
+        self.n_chunks = len(chunks)
+        # the kernels trust the table: check it covers [0, n) exactly, in
+        # order, before it reaches the device
+        pos = 0
+        for start, length, tensor in chunks:
+            assert start == pos and 0 < length <= chunk, (start, length)
+            assert 0 <= tensor < self.n_tensors
+            pos += length
+        assert pos == self.n
+        starts = torch.tensor([c[0] for c in chunks], dtype=torch.int64)
+        rest = torch.tensor([c[1:] for c in chunks], dtype=torch.int32)
+        table = torch.cat([starts.view(torch.int32).reshape(-1, 2), rest], 1)
+        self.chunks = table.contiguous().to(device)
+        first = [0] * (self.n_tensors + 1)
+        for _, _, tensor in chunks:
+            first[tensor + 1] += 1
+        for t in range(self.n_tensors):
+            first[t + 1] += first[t]
+        self.tensor_chunk = torch.tensor(first, dtype=torch.int32,
+                                         device=device)
+        self.wd = torch.empty(self.n_tensors, dtype=torch.float32,
+                              device=device)
+        self.lr_scale = torch.empty_like(self.wd)
+        self.lars_on = torch.empty(self.n_tensors, dtype=torch.int32,
+                                   device=device)
+        self.set_options(wd, lr_scale, lars_on)
+
+    def set_options(self, wd: tp.Sequence[float],
+                    lr_scale: tp.Sequence[float],
+                    lars_on: tp.Sequence[bool]) -> None:
+        """Overwrite the per-tensor values (one per tensor each) in place."""
+        if not len(wd) == len(lr_scale) == len(lars_on) == self.n_tensors:
+            raise ValueError(f"need {self.n_tensors} values per option")
+        self.wd.copy_(torch.tensor(list(wd), dtype=torch.float32))
+        self.lr_scale.copy_(torch.tensor(list(lr_scale), dtype=torch.float32))
+        self.lars_on.copy_(torch.tensor([int(bool(x)) for x in lars_on],
+                                        dtype=torch.int32))
+
+
+def _seg_check(table: SegTable, *buffers: tp.Optional[torch.Tensor]) -> None:
+    for t in buffers:
+        if t is None:
+            continue
+        assert t.is_cuda and t.is_contiguous() and t.numel() == table.n, \
+            "buffer does not match the chunk table"
+        assert t.device == table.chunks.device
+        # float4 / ushort4 accesses at flat indices that are multiples of 4
+        assert t.data_ptr() % (4 * t.element_size()) == 0, \
+            "vector accesses need an aligned buffer"
+
+
+def seg_sqsum(p: torch.Tensor, g: torch.Tensor, table: SegTable,
+              partials: torch.Tensor) -> None:
+    """Per-chunk ``(sum p^2, sum g^2)`` into the fp32 ``partials [C, 2]`` (no
+    atomics, no pre-zeroing: every slot is written, deterministic for a
+    given table).  Feed them to :func:`lars_prepare`."""
+    ext = require()
+    assert p.dtype == torch.float32 and g.dtype == torch.float32
+    _seg_check(table, p, g)
+    assert partials.dtype == torch.float32 and partials.is_contiguous()
+    assert partials.is_cuda and partials.numel() == 2 * table.n_chunks
+    ext.seg_sqsum(p.data_ptr(), g.data_ptr(), table.chunks.data_ptr(),
+                  table.n_chunks, partials.data_ptr(), _stream())
+
+
+def lars_prepare(partials: torch.Tensor, table: SegTable,
+                 ratio: torch.Tensor, eta: float, eps: float,
+                 grad_scale: float = 1.0,
+                 hyper: tp.Optional[torch.Tensor] = None) -> None:
+    """Write the LARS trust ratio of every tensor of ``table`` into the fp32
+    ``ratio [T]``: ``eta * |p| / (|g'| + wd * |p| + eps)`` with
+    ``g' = grad_scale * hyper[HYPER_COEF] * g`` where the tensor has LARS on
+    and both norms are positive, else 1.  The chunk partials are summed per
+    tensor in fixed order in fp64; no host read.  Run it after
+    :func:`optim_prepare` when ``hyper`` is given."""
+    ext = require()
+    assert partials.dtype == torch.float32 and partials.is_contiguous()
+    assert partials.is_cuda and partials.numel() == 2 * table.n_chunks
+    assert ratio.dtype == torch.float32 and ratio.is_contiguous()
+    assert ratio.is_cuda and ratio.numel() == table.n_tensors
+    ext.lars_prepare(partials.data_ptr(), table.tensor_chunk.data_ptr(),
+                     table.wd.data_ptr(), table.lars_on.data_ptr(),
+                     ratio.data_ptr(), table.n_tensors, _hyper_ptr(hyper),
+                     grad_scale, float(eta), float(eps), _stream())
+
+
+def fused_sgd_seg(p: torch.Tensor, g: torch.Tensor,
+                  m: tp.Optional[torch.Tensor], lr: float, momentum: float,
+                  table: SegTable, grad_scale: float = 1.0,
+                  nesterov: bool = False,
+                  p_bf16: tp.Optional[torch.Tensor] = None,
+                  hyper: tp.Optional[torch.Tensor] = None,
+                  ratio: tp.Optional[torch.Tensor] = None) -> None:
+    """:func:`fused_sgd` with ``wd`` and ``lr * lr_scale`` taken per tensor
+    from ``table`` and, when ``ratio`` (from :func:`lars_prepare`) is given,
+    the update scaled by the tensor's trust ratio."""
+    ext = require()
+    assert p.dtype == torch.float32 and g.dtype == torch.float32
+    _seg_check(table, p, g, m, p_bf16)
+    if ratio is not None:
+        assert ratio.dtype == torch.float32 and ratio.is_cuda
+        assert ratio.is_contiguous() and ratio.numel() == table.n_tensors
+    ext.fused_sgd_seg(p.data_ptr(), g.data_ptr(),
+                      m.data_ptr() if m is not None else 0,
+                      p_bf16.data_ptr() if p_bf16 is not None else 0,
+                      p.numel(), lr, momentum, grad_scale, nesterov,
+                      _hyper_ptr(hyper), table.chunks.data_ptr(),
+                      table.n_chunks, table.wd.data_ptr(),
+                      table.lr_scale.data_ptr(),
+                      ratio.data_ptr() if ratio is not None else 0, _stream())
+
+
+def fused_adam_seg(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
+                   v: torch.Tensor, lr: float, beta1: float, beta2: float,
+                   eps: float, step: int, table: SegTable,
+                   grad_scale: float = 1.0, adamw: bool = False,
+                   p_bf16: tp.Optional[torch.Tensor] = None,
+                   step_dev: tp.Optional[torch.Tensor] = None,
+                   hyper: tp.Optional[torch.Tensor] = None) -> None:
+    """:func:`fused_adam` with ``wd`` and ``lr * lr_scale`` taken per tensor
+    from ``table``."""
+    ext = require()
+    assert p.dtype == torch.float32 and g.dtype == torch.float32
+    _seg_check(table, p, g, m, v, p_bf16)
+    ext.fused_adam_seg(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                       p_bf16.data_ptr() if p_bf16 is not None else 0,
+                       step_dev.data_ptr() if step_dev is not None else 0,
+                       p.numel(), lr, beta1, beta2, eps, step, grad_scale,
+                       adamw, _hyper_ptr(hyper), table.chunks.data_ptr(),
+                       table.n_chunks, table.wd.data_ptr(),
+                       table.lr_scale.data_ptr(), _stream())
+
+
+# ---------------------------------------------------------------------------
 # input ingest (uint8 NHWC -> bf16 NHWC; see flashy_amd/data.py)
 # ---------------------------------------------------------------------------
 

@@ -95,6 +95,24 @@ void launch_optim_prepare(void* hyper, const void* partials, int n_partials,
                           double start_factor, int64_t total_steps,
                           double min_ratio, const int64_t* milestones,
                           int n_milestones, double gamma, hipStream_t stream);
+void launch_seg_sqsum(const void* p, const void* g, const void* chunks,
+                      int n_chunks, void* partials, hipStream_t stream);
+void launch_lars_prepare(const void* partials, const void* tensor_chunk,
+                         const void* wd, const void* lars_on, void* ratio,
+                         int n_tensors, const void* hyper, float grad_scale,
+                         double eta, double eps, hipStream_t stream);
+void launch_fused_sgd_seg(void* p, const void* g, void* m, void* p_bf16,
+                          int64_t n, float lr, float momentum,
+                          float grad_scale, int nesterov, const void* hyper,
+                          const void* chunks, int n_chunks, const void* wd,
+                          const void* lr_scale, const void* ratio,
+                          hipStream_t stream);
+void launch_fused_adam_seg(void* p, const void* g, void* m, void* v,
+                           void* p_bf16, void* step_dev, int64_t n, float lr,
+                           float beta1, float beta2, float eps, int64_t step,
+                           float grad_scale, int adamw, const void* hyper,
+                           const void* chunks, int n_chunks, const void* wd,
+                           const void* lr_scale, hipStream_t stream);
 void launch_image_ingest(const void* src, void* out, const void* step_dev,
                          int N, int H, int W, int OH, int OW, int pad,
                          uint64_t seed, uint32_t flip_thresh,
@@ -435,6 +453,59 @@ PYBIND11_MODULE(_hip_ops, m) {
                                    total_steps, min_ratio, milestones.data(),
                                    (int)milestones.size(), gamma,
                                    as_stream(stream));
+              check_last();
+          });
+    // segmented path (per-tensor wd / lr scale / LARS): `chunks` is the
+    // device chunk table, 16 bytes per entry; wd / lr_scale / lars_on / ratio
+    // are per-tensor arrays; tensor_chunk has one more entry than tensors
+    m.def("seg_sqsum",
+          [](uintptr_t p, uintptr_t g, uintptr_t chunks, int n_chunks,
+             uintptr_t partials, uintptr_t stream) {
+              launch_seg_sqsum((const void*)p, (const void*)g,
+                               (const void*)chunks, n_chunks, (void*)partials,
+                               as_stream(stream));
+              check_last();
+          });
+    m.def("lars_prepare",
+          [](uintptr_t partials, uintptr_t tensor_chunk, uintptr_t wd,
+             uintptr_t lars_on, uintptr_t ratio, int n_tensors,
+             uintptr_t hyper, float grad_scale, double eta, double eps,
+             uintptr_t stream) {
+              launch_lars_prepare((const void*)partials,
+                                  (const void*)tensor_chunk, (const void*)wd,
+                                  (const void*)lars_on, (void*)ratio,
+                                  n_tensors, (const void*)hyper, grad_scale,
+                                  eta, eps, as_stream(stream));
+              check_last();
+          });
+    m.def("fused_sgd_seg",
+          [](uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p_bf16,
+             int64_t n, float lr, float momentum, float grad_scale,
+             bool nesterov, uintptr_t hyper, uintptr_t chunks, int n_chunks,
+             uintptr_t wd, uintptr_t lr_scale, uintptr_t ratio,
+             uintptr_t stream) {
+              launch_fused_sgd_seg((void*)p, (const void*)g, (void*)mom,
+                                   (void*)p_bf16, n, lr, momentum, grad_scale,
+                                   nesterov ? 1 : 0, (const void*)hyper,
+                                   (const void*)chunks, n_chunks,
+                                   (const void*)wd, (const void*)lr_scale,
+                                   (const void*)ratio, as_stream(stream));
+              check_last();
+          });
+    m.def("fused_adam_seg",
+          [](uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t var,
+             uintptr_t p_bf16, uintptr_t step_dev, int64_t n, float lr,
+             float beta1, float beta2, float eps, int64_t step,
+             float grad_scale, bool adamw, uintptr_t hyper, uintptr_t chunks,
+             int n_chunks, uintptr_t wd, uintptr_t lr_scale,
+             uintptr_t stream) {
+              launch_fused_adam_seg((void*)p, (const void*)g, (void*)mom,
+                                    (void*)var, (void*)p_bf16, (void*)step_dev,
+                                    n, lr, beta1, beta2, eps, step, grad_scale,
+                                    adamw ? 1 : 0, (const void*)hyper,
+                                    (const void*)chunks, n_chunks,
+                                    (const void*)wd, (const void*)lr_scale,
+                                    as_stream(stream));
               check_last();
           });
     // uint8 NHWC -> bf16 NHWC crop / flip / normalize (csrc/ingest.hip);

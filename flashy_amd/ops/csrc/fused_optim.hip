@@ -373,3 +373,303 @@ extern "C" void launch_optim_prepare(void* hyper, const void* partials,
         (float*)hyper, (const float*)partials, n_partials,
         (const long long*)step_dev, max_norm, s);
 }
+
+// ---------------------------------------------------------------------------
+// Segmented path: per-tensor weight decay / lr scale / LARS trust ratio.
+//
+// The flat kernels above do not know where one tensor ends.  The host cuts
+// the arena once into CHUNKS: the intersection of a fixed window of
+// SEG_CHUNK elements (window w covers [w * SEG_CHUNK, (w + 1) * SEG_CHUNK) of
+// the flat index) with one tensor.  A chunk never crosses a tensor boundary,
+// an edge between two chunks of one tensor is a window edge (a multiple of 4),
+// and there are at most ceil(n / SEG_CHUNK) + T - 1 of them.  One block walks
+// one chunk at a time: scalar head up to 16-byte alignment, float4 body,
+// scalar tail.  The flat layout itself is untouched.
+//
+//   LARS (timm's Lars, trust_clip off), per tensor with lars on:
+//     g' = grad_scale * clip_coef * g
+//     ratio = eta * |p| / (|g'| + wd_t * |p| + eps)   if |p| > 0 and |g'| > 0
+//             1                                        otherwise
+//     d = ratio * (g' + wd_t * p)   then momentum as above, then
+//     p -= lr * lr_scale_t * d
+//   ratio = 1 is the plain SGD formula, so sgd_one is shared: the kernel
+//   hands it grad_scale * ratio and wd_t * ratio.
+// ---------------------------------------------------------------------------
+
+#define SEG_THREADS 256
+
+struct SegChunk {
+    long long start;  // flat index of the first element
+    int len;          // 1 .. SEG_CHUNK
+    int tensor;       // index into the per-tensor arrays
+};
+static_assert(sizeof(SegChunk) == 16, "one 16-byte table entry per chunk");
+
+struct SegArgs {
+    const SegChunk* __restrict__ chunks;
+    int n_chunks;
+    const float* __restrict__ wd;        // [T]
+    const float* __restrict__ lr_scale;  // [T]
+    const float* __restrict__ ratio;     // [T] trust ratios (null = all 1)
+};
+
+static inline int seg_grid(int n_chunks) {
+    return n_chunks < 1 ? 1 : (n_chunks > 2048 ? 2048 : n_chunks);
+}
+
+// `one(i)` handles flat element i, `four(i)` the aligned elements i .. i + 3
+template <typename One, typename Four>
+__device__ __forceinline__ void seg_walk(const SegChunk& c, One one,
+                                         Four four) {
+    const int to_align = (int)((4 - (c.start & 3)) & 3);
+    const int head = to_align < c.len ? to_align : c.len;
+    const int body4 = (c.len - head) >> 2;
+    const int tail = c.len - head - body4 * 4;
+    const int64_t body = c.start + head;
+    if ((int)threadIdx.x < head) one(c.start + threadIdx.x);
+#pragma unroll 4
+    for (int i = threadIdx.x; i < body4; i += SEG_THREADS)
+        four(body + 4 * (int64_t)i);
+    if ((int)threadIdx.x < tail)
+        one(body + 4 * (int64_t)body4 + threadIdx.x);
+}
+
+// (sum p^2, sum g^2) of every chunk.  No atomics, no pre-zeroing: every slot
+// is overwritten, deterministic for a given table.  A running fp32 sum sees at
+// most 6 terms (head, 4 float4 lanes at SEG_CHUNK = 4096, tail), then 2 lane,
+// 6 wave and 2 block steps.
+__global__ void __launch_bounds__(SEG_THREADS)
+k_seg_sqsum(const float* __restrict__ p, const float* __restrict__ g,
+            const SegChunk* __restrict__ chunks, int n_chunks,
+            float2* __restrict__ partials) {
+    __shared__ float2 wave_part[SEG_THREADS / WAVE_SIZE];
+    for (int ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {
+        const SegChunk c = chunks[ci];
+        float4 ap{0.f, 0.f, 0.f, 0.f}, ag{0.f, 0.f, 0.f, 0.f};
+        seg_walk(c,
+            [&](int64_t i) {
+                const float x = p[i], y = g[i];
+                ap.x += x * x;
+                ag.x += y * y;
+            },
+            [&](int64_t i) {
+                const float4 x = *reinterpret_cast<const float4*>(p + i);
+                const float4 y = *reinterpret_cast<const float4*>(g + i);
+                ap.x += x.x * x.x; ap.y += x.y * x.y;
+                ap.z += x.z * x.z; ap.w += x.w * x.w;
+                ag.x += y.x * y.x; ag.y += y.y * y.y;
+                ag.z += y.z * y.z; ag.w += y.w * y.w;
+            });
+        const float sp = wave_sum((ap.x + ap.y) + (ap.z + ap.w));
+        const float sg = wave_sum((ag.x + ag.y) + (ag.z + ag.w));
+        if ((threadIdx.x & (WAVE_SIZE - 1)) == 0)
+            wave_part[threadIdx.x / WAVE_SIZE] = float2{sp, sg};
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const float2 w0 = wave_part[0], w1 = wave_part[1];
+            const float2 w2 = wave_part[2], w3 = wave_part[3];
+            partials[ci] = float2{(w0.x + w1.x) + (w2.x + w3.x),
+                                  (w0.y + w1.y) + (w2.y + w3.y)};
+        }
+        __syncthreads();  // wave_part is reused by the next chunk
+    }
+}
+
+extern "C" void launch_seg_sqsum(const void* p, const void* g,
+                                 const void* chunks, int n_chunks,
+                                 void* partials, hipStream_t stream) {
+    k_seg_sqsum<<<seg_grid(n_chunks), SEG_THREADS, 0, stream>>>(
+        (const float*)p, (const float*)g, (const SegChunk*)chunks, n_chunks,
+        (float2*)partials);
+}
+
+// One wave per tensor: sum the tensor's chunk partials (chunks
+// tensor_chunk[t] .. tensor_chunk[t + 1]) in fixed order in fp64 and write the
+// trust ratio.  Runs after k_optim_prepare: the clip coefficient comes from the
+// hyper block, so clipping composes with LARS under graph replay.
+__global__ void __launch_bounds__(256)
+k_lars_prepare(const float2* __restrict__ partials,
+               const int* __restrict__ tensor_chunk,
+               const float* __restrict__ wd, const int* __restrict__ lars_on,
+               float* __restrict__ ratio, int n_tensors,
+               const float* __restrict__ hyper, float grad_scale, double eta,
+               double eps) {
+    const int t = blockIdx.x * (256 / WAVE_SIZE) + threadIdx.x / WAVE_SIZE;
+    const int lane = threadIdx.x & (WAVE_SIZE - 1);
+    if (t >= n_tensors) return;  // wave-uniform
+    const bool on = lars_on[t] != 0;
+    double sp = 0.0, sg = 0.0;
+    if (on) {
+        const int end = tensor_chunk[t + 1];
+        for (int c = tensor_chunk[t] + lane; c < end; c += WAVE_SIZE) {
+            const float2 v = partials[c];
+            sp += (double)v.x;
+            sg += (double)v.y;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            sp += __shfl_down(sp, off, WAVE_SIZE);
+            sg += __shfl_down(sg, off, WAVE_SIZE);
+        }
+    }
+    if (lane != 0) return;
+    double r = 1.0;
+    if (on) {
+        const double coef = hyper != nullptr ? (double)hyper[HYPER_COEF] : 1.0;
+        const double wn = sqrt(sp);
+        const double gn = fabs((double)grad_scale * coef) * sqrt(sg);
+        if (wn > 0.0 && gn > 0.0)
+            r = eta * wn / (gn + (double)wd[t] * wn + eps);
+    }
+    ratio[t] = (float)r;
+}
+
+extern "C" void launch_lars_prepare(const void* partials,
+                                    const void* tensor_chunk, const void* wd,
+                                    const void* lars_on, void* ratio,
+                                    int n_tensors, const void* hyper,
+                                    float grad_scale, double eta, double eps,
+                                    hipStream_t stream) {
+    const int per_block = 256 / WAVE_SIZE;
+    k_lars_prepare<<<(n_tensors + per_block - 1) / per_block, 256, 0, stream>>>(
+        (const float2*)partials, (const int*)tensor_chunk, (const float*)wd,
+        (const int*)lars_on, (float*)ratio, n_tensors, (const float*)hyper,
+        grad_scale, eta, eps);
+}
+
+template <bool HAS_M, bool HAS_BF16>
+__global__ void __launch_bounds__(SEG_THREADS)
+k_fused_sgd_seg(SgdArgs a, SegArgs s) {
+    if (a.hyper != nullptr) {
+        a.lr = a.hyper[HYPER_LR];
+        a.grad_scale *= a.hyper[HYPER_COEF];
+    }
+    const float lr = a.lr, grad_scale = a.grad_scale;
+    for (int ci = blockIdx.x; ci < s.n_chunks; ci += gridDim.x) {
+        const SegChunk c = s.chunks[ci];
+        const float r = s.ratio != nullptr ? s.ratio[c.tensor] : 1.f;
+        a.lr = lr * s.lr_scale[c.tensor];
+        a.wd = s.wd[c.tensor] * r;
+        a.grad_scale = grad_scale * r;
+        seg_walk(c,
+            [&](int64_t i) {
+                float m = HAS_M ? a.m[i] : 0.f;
+                const float p = sgd_one(a, a.p[i], a.g[i], m);
+                a.p[i] = p;
+                if (HAS_M) a.m[i] = m;
+                if (HAS_BF16) a.p_bf16[i] = f32_to_bf16(p);
+            },
+            [&](int64_t i) {
+                float4 p = *reinterpret_cast<float4*>(a.p + i);
+                const float4 g = *reinterpret_cast<const float4*>(a.g + i);
+                float4 m = HAS_M ? *reinterpret_cast<float4*>(a.m + i)
+                                 : float4{0, 0, 0, 0};
+                p.x = sgd_one(a, p.x, g.x, m.x);
+                p.y = sgd_one(a, p.y, g.y, m.y);
+                p.z = sgd_one(a, p.z, g.z, m.z);
+                p.w = sgd_one(a, p.w, g.w, m.w);
+                *reinterpret_cast<float4*>(a.p + i) = p;
+                if (HAS_M) *reinterpret_cast<float4*>(a.m + i) = m;
+                if (HAS_BF16) {
+                    ushort4 b;
+                    b.x = f32_to_bf16(p.x); b.y = f32_to_bf16(p.y);
+                    b.z = f32_to_bf16(p.z); b.w = f32_to_bf16(p.w);
+                    *reinterpret_cast<ushort4*>(a.p_bf16 + i) = b;
+                }
+            });
+    }
+}
+
+extern "C" void launch_fused_sgd_seg(void* p, const void* g, void* m,
+                                     void* p_bf16, int64_t n, float lr,
+                                     float momentum, float grad_scale,
+                                     int nesterov, const void* hyper,
+                                     const void* chunks, int n_chunks,
+                                     const void* wd, const void* lr_scale,
+                                     const void* ratio, hipStream_t stream) {
+    SgdArgs a{(float*)p, (const float*)g, (float*)m, (uint16_t*)p_bf16,
+              n, lr, momentum, 0.f, grad_scale, nesterov, (const float*)hyper};
+    SegArgs s{(const SegChunk*)chunks, n_chunks, (const float*)wd,
+              (const float*)lr_scale, (const float*)ratio};
+    const int grid = seg_grid(n_chunks);
+    if (m != nullptr && p_bf16 != nullptr)
+        k_fused_sgd_seg<true, true><<<grid, SEG_THREADS, 0, stream>>>(a, s);
+    else if (m != nullptr)
+        k_fused_sgd_seg<true, false><<<grid, SEG_THREADS, 0, stream>>>(a, s);
+    else if (p_bf16 != nullptr)
+        k_fused_sgd_seg<false, true><<<grid, SEG_THREADS, 0, stream>>>(a, s);
+    else
+        k_fused_sgd_seg<false, false><<<grid, SEG_THREADS, 0, stream>>>(a, s);
+}
+
+template <bool HAS_BF16>
+__global__ void __launch_bounds__(SEG_THREADS)
+k_fused_adam_seg(AdamArgs a, SegArgs s) {
+    if (a.step_ptr != nullptr) {
+        const float t = (float)*a.step_ptr;
+        a.bc1 = 1.f - powf(a.beta1, t);
+        a.bc2 = 1.f - powf(a.beta2, t);
+    }
+    if (a.hyper != nullptr) {
+        a.lr = a.hyper[HYPER_LR];
+        a.grad_scale *= a.hyper[HYPER_COEF];
+    }
+    const float lr = a.lr;
+    for (int ci = blockIdx.x; ci < s.n_chunks; ci += gridDim.x) {
+        const SegChunk c = s.chunks[ci];
+        a.lr = lr * s.lr_scale[c.tensor];
+        a.wd = s.wd[c.tensor];
+        seg_walk(c,
+            [&](int64_t i) {
+                float m = a.m[i], v = a.v[i];
+                const float p = adam_one(a, a.p[i], a.g[i], m, v);
+                a.p[i] = p;
+                a.m[i] = m;
+                a.v[i] = v;
+                if (HAS_BF16) a.p_bf16[i] = f32_to_bf16(p);
+            },
+            [&](int64_t i) {
+                float4 p = *reinterpret_cast<float4*>(a.p + i);
+                const float4 g = *reinterpret_cast<const float4*>(a.g + i);
+                float4 m = *reinterpret_cast<float4*>(a.m + i);
+                float4 v = *reinterpret_cast<float4*>(a.v + i);
+                p.x = adam_one(a, p.x, g.x, m.x, v.x);
+                p.y = adam_one(a, p.y, g.y, m.y, v.y);
+                p.z = adam_one(a, p.z, g.z, m.z, v.z);
+                p.w = adam_one(a, p.w, g.w, m.w, v.w);
+                *reinterpret_cast<float4*>(a.p + i) = p;
+                *reinterpret_cast<float4*>(a.m + i) = m;
+                *reinterpret_cast<float4*>(a.v + i) = v;
+                if (HAS_BF16) {
+                    ushort4 b;
+                    b.x = f32_to_bf16(p.x); b.y = f32_to_bf16(p.y);
+                    b.z = f32_to_bf16(p.z); b.w = f32_to_bf16(p.w);
+                    *reinterpret_cast<ushort4*>(a.p_bf16 + i) = b;
+                }
+            });
+    }
+}
+
+extern "C" void launch_fused_adam_seg(void* p, const void* g, void* m, void* v,
+                                      void* p_bf16, void* step_dev, int64_t n,
+                                      float lr, float beta1, float beta2,
+                                      float eps, int64_t step,
+                                      float grad_scale, int adamw,
+                                      const void* hyper, const void* chunks,
+                                      int n_chunks, const void* wd,
+                                      const void* lr_scale,
+                                      hipStream_t stream) {
+    AdamArgs a{(float*)p, (const float*)g, (float*)m, (float*)v,
+               (uint16_t*)p_bf16, (const long long*)step_dev,
+               (const float*)hyper, n, lr, beta1,
+               beta2, eps, 0.f,
+               1.f - powf(beta1, (float)step), 1.f - powf(beta2, (float)step),
+               grad_scale, adamw};
+    SegArgs s{(const SegChunk*)chunks, n_chunks, (const float*)wd,
+              (const float*)lr_scale, nullptr};
+    const int grid = seg_grid(n_chunks);
+    if (p_bf16 != nullptr)
+        k_fused_adam_seg<true><<<grid, SEG_THREADS, 0, stream>>>(a, s);
+    else
+        k_fused_adam_seg<false><<<grid, SEG_THREADS, 0, stream>>>(a, s);
+}

@@ -28,6 +28,13 @@ counter and the gradient arena, and the update kernels read them from
 memory.  A step captured into a HIP graph therefore follows the schedule and
 clips, with no re-capture and no host sync.  :class:`LRSchedule` objects are
 the host mirror of the same closed forms.
+
+Per-tensor hyperparameters (``param_options=`` / torch-style param groups) and
+LARS trust ratios (``FusedSGD(..., lars=LARS())``) ride on a chunk table that
+tells the kernels where each tensor lies in the flat buffer; the layout of
+the buffer itself never changes, and an optimizer built without them launches
+exactly the unsegmented kernels.  The trust ratios are computed on the device
+from the hyper block, so they too are correct under graph replay.
 """
 from __future__ import annotations
 
@@ -39,7 +46,11 @@ import torch
 
 from . import ops
 
-ParamsT = tp.Iterable[torch.nn.Parameter]
+ParamsT = tp.Union[tp.Iterable[torch.nn.Parameter],
+                   tp.Iterable[tp.Mapping[str, tp.Any]]]
+ParamOptionsT = tp.Union[
+    tp.Callable[[torch.nn.Parameter], tp.Optional[tp.Mapping[str, tp.Any]]],
+    tp.Mapping[torch.nn.Parameter, tp.Mapping[str, tp.Any]]]
 
 MAX_MILESTONES = 8
 
@@ -171,6 +182,84 @@ class MultiStep(LRSchedule):
         return self._warm(step) * math.pow(self.gamma, float(passed))
 
 
+# ---------------------------------------------------------------------------
+# Per-tensor options and LARS
+# ---------------------------------------------------------------------------
+
+@dataclasses.dataclass(frozen=True)
+class LARS:
+    """Layer-wise adaptive rate scaling (timm's ``Lars``, ``trust_clip`` off):
+    a tensor's update is multiplied by
+    ``eta * |p| / (|g| + weight_decay * |p| + eps)``, or by 1 where either
+    norm is 0."""
+    eta: float = 1e-3
+    eps: float = 1e-8
+
+    def __post_init__(self):
+        if not self.eta > 0:
+            raise ValueError(f"eta must be > 0: {self.eta}")
+        if self.eps < 0:
+            raise ValueError(f"eps must be >= 0: {self.eps}")
+
+
+OPTION_KEYS = ("weight_decay", "lr_scale", "lars")
+_GROUP_KEYS = ("params", "weight_decay", "lr", "lars")
+
+
+def no_decay_1d(p: torch.nn.Parameter) -> tp.Dict[str, tp.Any]:
+    """``param_options`` callable for the usual BatchNorm / bias exemption:
+    no weight decay and no LARS on tensors with ``ndim <= 1``."""
+    if p.ndim <= 1:
+        return {"weight_decay": 0.0, "lars": False}
+    return {}
+
+
+def _checked_options(raw: tp.Optional[tp.Mapping[str, tp.Any]]
+                     ) -> tp.Dict[str, tp.Any]:
+    """One tensor's options; ``None`` for weight_decay / lars means "use the
+    optimizer's value"."""
+    raw = raw or {}
+    unknown = sorted(set(raw) - set(OPTION_KEYS))
+    if unknown:
+        raise ValueError(f"unknown param option(s) {unknown}; "
+                         f"known: {list(OPTION_KEYS)}")
+    wd = raw.get("weight_decay")
+    lars = raw.get("lars")
+    return {"weight_decay": None if wd is None else float(wd),
+            "lr_scale": float(raw.get("lr_scale", 1.0)),
+            "lars": None if lars is None else bool(lars)}
+
+
+def _unpack_param_groups(groups: tp.Sequence[tp.Mapping[str, tp.Any]],
+                         default_lr: float):
+    """torch-style param groups -> (parameters in order of appearance,
+    {id(param): options})."""
+    params: tp.List[torch.nn.Parameter] = []
+    options: tp.Dict[int, tp.Dict[str, tp.Any]] = {}
+    for group in groups:
+        if not isinstance(group, tp.Mapping) or "params" not in group:
+            raise ValueError("a param group is a dict with a 'params' entry")
+        unknown = sorted(set(group) - set(_GROUP_KEYS))
+        if unknown:
+            raise ValueError(f"unknown param group key(s) {unknown}; "
+                             f"known: {list(_GROUP_KEYS)}")
+        opts = {k: group[k] for k in ("weight_decay", "lars") if k in group}
+        if "lr" in group:
+            if default_lr == 0:
+                raise ValueError("a group lr needs a non-zero default lr")
+            opts["lr_scale"] = group["lr"] / default_lr
+        members = group["params"]
+        if isinstance(members, torch.Tensor):
+            members = [members]
+        for p in members:
+            if id(p) in options:
+                raise ValueError(
+                    "some parameters appear in more than one parameter group")
+            options[id(p)] = opts
+            params.append(p)
+    return params, options
+
+
 class _Group:
     """One (device, dtype) flat group."""
 
@@ -202,6 +291,13 @@ class _Group:
         # optimizer kernel in the same pass as the update; modules read the
         # per-param view via `param._bf16_mirror` (flashy_amd/nn.py) so the
         # step needs zero weight-cast kernels.
+        # per-tensor options (one dict per param, see _checked_options), and
+        # when they make the step segmented: the device chunk table, the
+        # per-chunk (sum p^2, sum g^2) workspace and the trust ratios
+        self.options: tp.List[tp.Dict[str, tp.Any]] = []
+        self.seg: tp.Optional[ops.SegTable] = None
+        self.seg_partials: tp.Optional[torch.Tensor] = None
+        self.ratio: tp.Optional[torch.Tensor] = None
         self.flat_p16: tp.Optional[torch.Tensor] = None
         if bf16_mirror:
             self.flat_p16 = self.flat_p.to(torch.bfloat16)
@@ -220,18 +316,45 @@ class _Group:
 
 
 class FlatOptimizer:
-    """Base: flat parameter/grad packing + state dict plumbing."""
+    """Base: flat parameter/grad packing + state dict plumbing.
+
+    ``params`` is an iterable of parameters or a list of torch-style param
+    groups (``{"params": [...], "weight_decay": ..., "lr": ..., "lars":
+    ...}``, packed in order of appearance; a group ``lr`` becomes
+    ``lr_scale = lr / default lr``).  Prefer ``param_options``: a callable
+    ``(param) -> options or None`` or a mapping ``param -> options`` with the
+    keys ``weight_decay``, ``lr_scale`` and ``lars``, which keeps the
+    parameters packed in the model's own order (e.g.
+    ``param_options=no_decay_1d``)."""
+
+    _SUPPORTS_LARS = False
 
     def __init__(self, params: ParamsT, defaults: tp.Dict[str, tp.Any],
                  bf16_mirror: bool = False,
                  schedule: tp.Optional[LRSchedule] = None,
-                 max_grad_norm: tp.Optional[float] = None):
+                 max_grad_norm: tp.Optional[float] = None,
+                 param_options: tp.Optional[ParamOptionsT] = None,
+                 lars: tp.Optional[LARS] = None):
         if schedule is not None and not isinstance(schedule, LRSchedule):
             raise TypeError(f"schedule must be an LRSchedule, got {schedule!r}")
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError(
                 f"max_grad_norm must be > 0 or None, got {max_grad_norm}")
-        params = [p for p in params if p.requires_grad]
+        if lars is not None and not isinstance(lars, LARS):
+            raise TypeError(f"lars must be a LARS, got {lars!r}")
+        if lars is not None and not self._SUPPORTS_LARS:
+            raise NotImplementedError(
+                f"{type(self).__name__} has no LARS (LAMB needs the norm of "
+                f"the update); use FusedSGD(..., lars=LARS())")
+        params = list(params)
+        group_options: tp.Dict[int, tp.Dict[str, tp.Any]] = {}
+        if params and isinstance(params[0], tp.Mapping):
+            if param_options is not None:
+                raise ValueError(
+                    "give either param groups or param_options, not both")
+            params, group_options = _unpack_param_groups(
+                params, defaults["lr"])
+        params =[p for p in params if p.requires_grad]
         if not params:
             raise ValueError("no trainable parameters")
         for p in params:
@@ -243,6 +366,22 @@ class FlatOptimizer:
             by_key.setdefault((p.device, p.dtype), []).append(p)
         self.groups = [_Group(ps, bf16_mirror) for ps in by_key.values()]
         self.defaults = dict(defaults)
+        self.lars = lars
+
+        def options_of(p: torch.nn.Parameter) -> tp.Dict[str, tp.Any]:
+            if id(p) in group_options:
+                raw = group_options[id(p)]
+            elif param_options is None:
+                raw = None
+            elif isinstance(param_options, tp.Mapping):
+                raw = param_options.get(p)
+            else:
+                raw = param_options(p)
+            return _checked_options(raw)
+
+        for g in self.groups:
+            g.options = [options_of(p) for p in g.params]
+        self._segmented = False
         self.step_count = 0
         self._use_hip = any(g.device.type == "cuda" for g in self.groups)
         if self._use_hip:
@@ -264,6 +403,62 @@ class FlatOptimizer:
         self._host_norm: tp.Optional[torch.Tensor] = None
         if self._managed:
             self._init_managed()
+        self._configure_segments()
+
+    # -- per-tensor options --------------------------------------------------
+    def _resolved(self, group: _Group
+                  ) -> tp.List[tp.Tuple[float, float, bool]]:
+        """(weight_decay, lr_scale, lars) per tensor of ``group``."""
+        wd = self.defaults["weight_decay"]
+        return [(wd if o["weight_decay"] is None else o["weight_decay"],
+                 o["lr_scale"],
+                 self.lars is not None if o["lars"] is None else o["lars"])
+                for o in group.options]
+
+    def _configure_segments(self) -> None:
+        """Decide whether the step is segmented (some tensor's options differ
+        from the defaults, or LARS is on for some tensor) and build or
+        refresh the chunk tables.  Values are rewritten in place, so a
+        captured step sees restored options."""
+        resolved = [self._resolved(g) for g in self.groups]
+        wd = self.defaults["weight_decay"]
+        uses_lars = any(r[2] for rs in resolved for r in rs)
+        if uses_lars and not self._SUPPORTS_LARS:
+            raise NotImplementedError(
+                f"'lars': True on {type(self).__name__}: LARS is implemented "
+                f"for FusedSGD only")
+        if uses_lars and self.lars is None:
+            raise ValueError("'lars': True needs lars=LARS(...) on the "
+                             "optimizer")
+        self._segmented = uses_lars or any(
+            r[0] != wd or r[1] != 1.0 for rs in resolved for r in rs)
+        if not self._segmented:
+            return
+        for g, rs in zip(self.groups, resolved):
+            cols = list(zip(*rs))
+            if g.device.type == "cuda":
+                if g.seg is None:
+                    g.seg = ops.SegTable([p.numel() for p in g.params],
+                                         *cols, device=g.device)
+                else:
+                    g.seg.set_options(*cols)
+            if uses_lars and g.ratio is None:
+                g.ratio = torch.ones(len(g.params), dtype=torch.float32,
+                                     device=g.device)
+                if g.seg is not None:
+                    g.seg_partials = torch.empty(
+                        g.seg.n_chunks, 2, dtype=torch.float32,
+                        device=g.device)
+
+    @property
+    def last_trust_ratios(self) -> tp.Optional[tp.List[torch.Tensor]]:
+        """LARS trust ratios of the last step: one fp32 tensor per flat group
+        (see ``param_buffers``), on that group's device, one entry per
+        parameter in packing order (1 where LARS is off or a norm is 0).  No
+        sync.  ``None`` without LARS."""
+        if not any(g.ratio is not None for g in self.groups):
+            return None
+        return [g.ratio for g in self.groups]
 
     def _init_managed(self) -> None:
         devices = []
@@ -411,10 +606,29 @@ class FlatOptimizer:
             "defaults": dict(self.defaults),
             "step_count": self.step_count,
             "extra": self._extra_state(),
+            # per flat group, per tensor in packing order; weight_decay None
+            # = the optimizer's value
+            "param_options": [
+                [{"numel": p.numel(), "weight_decay": o["weight_decay"],
+                  "lr_scale": o["lr_scale"], "lars": r[2]}
+                 for p, o, r in zip(g.params, g.options, self._resolved(g))]
+                for g in self.groups],
         }
 
     def load_state_dict(self, state: tp.Mapping[str, tp.Any]) -> None:
+        saved = state.get("param_options")  # absent in older checkpoints
+        if saved is not None:
+            if [[o["numel"] for o in opts] for opts in saved] != \
+                    [[p.numel() for p in g.params] for g in self.groups]:
+                raise ValueError(
+                    "saved param_options do not match this optimizer's "
+                    "tensors (count or sizes differ)")
         self.defaults.update(state.get("defaults", {}))
+        if saved is not None:
+            for g, opts in zip(self.groups, saved):
+                g.options = [_checked_options(
+                    {k: o[k] for k in OPTION_KEYS}) for o in opts]
+            self._configure_segments()
         self.step_count = state.get("step_count", 0)
         self._load_extra_state(state.get("extra", {}))
         for dev_step in self._step_dev.values():
@@ -426,17 +640,34 @@ class FlatOptimizer:
 
 class FusedSGD(FlatOptimizer):
     """torch.optim.SGD semantics (momentum / weight decay / nesterov) as one
-    fused HIP kernel over the flat buffers."""
+    fused HIP kernel over the flat buffers.
+
+    ``param_options`` / param groups: see :class:`FlatOptimizer`.  With
+    ``lars=LARS(eta, eps)`` every tensor whose ``lars`` option is not False
+    is updated as, with ``g' = clip_coef * g``::
+
+        ratio = eta * |p| / (|g'| + wd_t * |p| + eps)  if |p| > 0 and |g'| > 0
+                1                                       otherwise
+        d = ratio * (g' + wd_t * p)
+        m = mu * m + d ; d = nesterov ? d + mu * m : m       (if momentum)
+        p -= lr * lr_scale_t * d
+
+    and the others (``ratio = 1``) by the plain SGD formula.  The norms are
+    taken on the device each step (``last_trust_ratios``)."""
+
+    _SUPPORTS_LARS = True
 
     def __init__(self, params: ParamsT, lr: float, momentum: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False,
                  bf16_mirror: bool = False,
                  schedule: tp.Optional[LRSchedule] = None,
-                 max_grad_norm: tp.Optional[float] = None):
+                 max_grad_norm: tp.Optional[float] = None,
+                 param_options: tp.Optional[ParamOptionsT] = None,
+                 lars: tp.Optional[LARS] = None):
         super().__init__(params, dict(lr=lr, momentum=momentum,
                                       weight_decay=weight_decay,
                                       nesterov=nesterov), bf16_mirror,
-                         schedule, max_grad_norm)
+                         schedule, max_grad_norm, param_options, lars)
         self._momentum_buffers = [
             g.buffers_like() if momentum != 0 else None for g in self.groups]
         if schedule is not None:
@@ -447,6 +678,9 @@ class FusedSGD(FlatOptimizer):
     def _step_group(self, group: _Group) -> None:
         d = self.defaults
         m = self._momentum_buffers[self.groups.index(group)]
+        if self._segmented:
+            self._step_group_segmented(group, m)
+            return
         if group.device.type == "cuda":
             ops.fused_sgd(group.flat_p, group.flat_g, m, d["lr"],
                           d["momentum"], d["weight_decay"],
@@ -467,6 +701,53 @@ class FusedSGD(FlatOptimizer):
             group.flat_p.add_(g, alpha=-lr)
             group.refresh_bf16()
 
+    def _step_group_segmented(self, group: _Group,
+                              m: tp.Optional[torch.Tensor]) -> None:
+        d = self.defaults
+        if group.device.type == "cuda":
+            hyper = self._hyper.get(group.device)
+            if group.ratio is not None:
+                ops.seg_sqsum(group.flat_p, group.flat_g, group.seg,
+                              group.seg_partials)
+                ops.lars_prepare(group.seg_partials, group.seg, group.ratio,
+                                 self.lars.eta, self.lars.eps, hyper=hyper)
+            ops.fused_sgd_seg(group.flat_p, group.flat_g, m, d["lr"],
+                              d["momentum"], group.seg,
+                              nesterov=d["nesterov"], p_bf16=group.flat_p16,
+                              hyper=hyper, ratio=group.ratio)
+            return
+        # CPU fallback: the same math, tensor by tensor
+        lr, coef = self._lr_coef()
+        with torch.no_grad():
+            offset = 0
+            for t, (p, (wd, lr_scale, lars_on)) in enumerate(
+                    zip(group.params, self._resolved(group))):
+                n = p.numel()
+                w = group.flat_p[offset:offset + n]
+                g = group.flat_g[offset:offset + n]
+                if coef is not None:
+                    g = g * coef
+                ratio = 1.0
+                if lars_on:
+                    wn = float(w.double().norm())
+                    gn = float(g.double().norm())
+                    if wn > 0 and gn > 0:
+                        ratio = self.lars.eta * wn / (
+                            gn + wd * wn + self.lars.eps)
+                if group.ratio is not None:
+                    group.ratio[t] = ratio
+                if wd != 0:
+                    g = g.add(w, alpha=wd)
+                if ratio != 1.0:
+                    g = g * ratio
+                if d["momentum"] != 0:
+                    mt = m[offset:offset + n]
+                    mt.mul_(d["momentum"]).add_(g)
+                    g = g.add(mt, alpha=d["momentum"]) if d["nesterov"] else mt
+                w.add_(g, alpha=-lr * lr_scale)
+                offset += n
+            group.refresh_bf16()
+
     def _extra_state(self):
         return {"momentum_buffers": self._momentum_buffers}
 
@@ -479,18 +760,24 @@ class FusedSGD(FlatOptimizer):
 
 
 class FusedAdam(FlatOptimizer):
-    """torch.optim.Adam/AdamW semantics as one fused HIP kernel per group."""
+    """torch.optim.Adam/AdamW semantics as one fused HIP kernel per group.
+
+    ``param_options`` / param groups: see :class:`FlatOptimizer`
+    (``weight_decay`` and ``lr_scale`` per tensor).  LARS is not implemented
+    here: ``lars=`` and ``'lars': True`` raise ``NotImplementedError``."""
 
     def __init__(self, params: ParamsT, lr: float = 1e-3,
                  betas: tp.Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.0,
                  adamw: bool = False, bf16_mirror: bool = False,
                  schedule: tp.Optional[LRSchedule] = None,
-                 max_grad_norm: tp.Optional[float] = None):
+                 max_grad_norm: tp.Optional[float] = None,
+                 param_options: tp.Optional[ParamOptionsT] = None,
+                 lars: tp.Optional[LARS] = None):
         super().__init__(params, dict(lr=lr, beta1=betas[0], beta2=betas[1],
                                       eps=eps, weight_decay=weight_decay,
                                       adamw=adamw), bf16_mirror,
-                         schedule, max_grad_norm)
+                         schedule, max_grad_norm, param_options, lars)
         self._exp_avg = [g.buffers_like() for g in self.groups]
         self._exp_avg_sq = [g.buffers_like() for g in self.groups]
         # device-side step counter: the kernel reads it for bias correction,
@@ -503,6 +790,14 @@ class FusedAdam(FlatOptimizer):
         d = self.defaults
         i = self.groups.index(group)
         m, v = self._exp_avg[i], self._exp_avg_sq[i]
+        if self._segmented and group.device.type == "cuda":
+            ops.fused_adam_seg(group.flat_p, group.flat_g, m, v, d["lr"],
+                               d["beta1"], d["beta2"], d["eps"],
+                               self.step_count, group.seg, adamw=d["adamw"],
+                               p_bf16=group.flat_p16,
+                               step_dev=self._step_dev[group.device],
+                               hyper=self._hyper.get(group.device))
+            return
         if group.device.type == "cuda":
             ops.fused_adam(group.flat_p, group.flat_g, m, v, d["lr"],
                            d["beta1"], d["beta2"], d["eps"],
@@ -512,6 +807,9 @@ class FusedAdam(FlatOptimizer):
                            hyper=self._hyper.get(group.device))
             return
         lr, coef = self._lr_coef()
+        if self._segmented:
+            self._step_group_segmented_cpu(group, m, v, lr, coef)
+            return
         with torch.no_grad():
             g = group.flat_g
             p = group.flat_p
@@ -527,6 +825,31 @@ class FusedAdam(FlatOptimizer):
             bc2 = 1 - d["beta2"] ** self.step_count
             denom = (v / bc2).sqrt_().add_(d["eps"])
             p.addcdiv_(m / bc1, denom, value=-lr)
+            group.refresh_bf16()
+
+    def _step_group_segmented_cpu(self, group, m, v, lr, coef) -> None:
+        """The same math as above, tensor by tensor."""
+        d = self.defaults
+        bc1 = 1 - d["beta1"] ** self.step_count
+        bc2 = 1 - d["beta2"] ** self.step_count
+        with torch.no_grad():
+            offset = 0
+            for param, (wd, lr_scale, _) in zip(group.params,
+                                                self._resolved(group)):
+                sl = slice(offset, offset + param.numel())
+                offset = sl.stop
+                p, g, mt, vt = group.flat_p[sl], group.flat_g[sl], m[sl], v[sl]
+                lr_t = lr * lr_scale
+                if coef is not None:
+                    g = g * coef
+                if d["adamw"]:
+                    p.mul_(1 - lr_t * wd)
+                elif wd != 0:
+                    g = g.add(p, alpha=wd)
+                mt.mul_(d["beta1"]).add_(g, alpha=1 - d["beta1"])
+                vt.mul_(d["beta2"]).addcmul_(g, g, value=1 - d["beta2"])
+                denom = (vt / bc2).sqrt_().add_(d["eps"])
+                p.addcdiv_(mt / bc1, denom, value=-lr_t)
             group.refresh_bf16()
 
     def _extra_state(self):
