@@ -714,7 +714,11 @@ def conv_dgrad(dout: torch.Tensor, w_rsck: torch.Tensor, dx: torch.Tensor,
     rsk = d.R * d.S * d.K
     stages = (rsk + 63) // 64
     zn = 0
-    if not ext.conv8_eligible(*d, True):
+    # stride 2: a form without zero-filled MFMA work (parity classes, 1x1
+    # quarter GEMM) runs single pass; split-K is for what that plan declines
+    if d.stride == 2 and ext.conv_dgrad_s2_plan(*d)[0]:
+        pass
+    elif not ext.conv8_eligible(*d, True):
         zn = _splitk_plan(M, d.C // 64, stages)
         if zn == 0 and d.stride == 1:
             zn = _underfill_zn(M, d.C, stages)
@@ -729,6 +733,30 @@ def conv_dgrad(dout: torch.Tensor, w_rsck: torch.Tensor, dx: torch.Tensor,
     else:
         ext.conv_dgrad(dout.data_ptr(), w_rsck.data_ptr(), dx.data_ptr(), *d,
                        _stream())
+
+
+DGRAD_S2_FORMS = {"generic": 0, "par8": 1, "par4": 2, "scat2": 3}
+
+
+def conv_dgrad_s2_plan(d: ConvDims) -> tp.Tuple[str, int]:
+    """(form, tile) the stride-2 dgrad plan picks for ``d``: "par8" (8-wave
+    parity classes, tile = BN), "par4" (4-wave parity classes, tile = BM),
+    "scat2" (1x1 quarter GEMM, tile = BN) or ("none", 0)."""
+    form, tile = require().conv_dgrad_s2_plan(*d)
+    names = {v: k for k, v in DGRAD_S2_FORMS.items() if v}
+    return names.get(form, "none"), tile
+
+
+def conv_dgrad_s2_form(dout: torch.Tensor, w_rsck: torch.Tensor,
+                       dx: torch.Tensor, d: ConvDims, form: str,
+                       tile: int) -> None:
+    """Stride-2 dgrad through one named form, whatever the plan would pick
+    (tests and scripts/dgrad_s2_sweep.py): "par8" / "par4" / "scat2" as in
+    :func:`conv_dgrad_s2_plan`, or "generic" (the zero-filled single-pass
+    kernels, ``tile`` ignored); raises where the form cannot run the shape."""
+    require().conv_dgrad_s2_form(dout.data_ptr(), w_rsck.data_ptr(),
+                                 dx.data_ptr(), *d, DGRAD_S2_FORMS[form],
+                                 tile, _stream())
 
 
 def weight_transpose_batched(src: torch.Tensor, dst: torch.Tensor,

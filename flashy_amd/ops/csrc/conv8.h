@@ -1,7 +1,7 @@
 // Copyright (c) Flashy-AMD authors.
 // Shared host side of the 8-wave deep-pipeline conv family for gfx950:
 // k_conv_fwd8 / k_conv1x1_mloop (conv_fwd8.hip), k_conv_dedup
-// (conv_dedup.hip) and k_conv_dgrad8 with its SCAT2 and split-K variants
+// (conv_dedup.hip) and k_conv_dgrad8 with its SCAT2, PAR2 and split-K variants
 // (conv_dgrad8.hip): the out-of-range sentinel, the family's off switch,
 // the BN choice, the runtime -> template dispatch helper and the prototypes
 // of every plan and launcher.
@@ -67,6 +67,21 @@ inline void dispatch8(int bn, bool flag, F&& f) {
     }
 }
 
+// Stride-2 dgrad forms (conv_dgrad_s2_plan; conv_dgrad.hip): 8-wave parity
+// classes (k_conv_dgrad8 PAR2, tile = BN), 4-wave parity classes
+// (k_conv_dgrad_s2, tile = BM), 1x1 quarter GEMM + sibling zeros (SCAT2,
+// tile = BN), or none of them (generic zero-filled kernel, split-K allowed).
+enum DgradS2Form {
+    DGRAD_S2_NONE = 0,
+    DGRAD_S2_PAR8 = 1,
+    DGRAD_S2_PAR4 = 2,
+    DGRAD_S2_SCAT2 = 3,
+};
+// Block floor of the 8-wave parity form, all four classes counted
+// (profiles/r05a_dgrad_s2_sweep.txt: it wins from 208 blocks up, the 4-wave
+// 32-row tile below)
+constexpr int kPar8Floor = 208;
+
 // Plans return grid.x (0 = not eligible) and are decided purely from the
 // dims; launchers take what the plan returned.
 extern "C" {
@@ -90,6 +105,15 @@ int conv_dgrad8_plan(ConvDims d, int* bn_out);
 void launch_conv_dgrad8(const void* dout, const void* w_rsck, void* dx,
                         ConvDims d, int bn, int mtiles, hipStream_t stream);
 int conv_dgrad8_s2_plan(ConvDims d, int* bn_out);
+int conv_dgrad8_s2_mtiles(ConvDims d);
+int conv_dgrad8_par2_mtiles(ConvDims d);
+void launch_conv_dgrad8_par2(const void* dout, const void* w_rsck, void* dx,
+                             ConvDims d, int bn, int mtiles,
+                             hipStream_t stream);
+int conv_dgrad_s2_plan(ConvDims d, int* tile_out);
+int launch_conv_dgrad_s2_form(const void* dout, const void* w_rsck, void* dx,
+                              ConvDims d, int form, int tile,
+                              hipStream_t stream);
 void launch_conv_dgrad8_s2(const void* dout, const void* w_rsck, void* dx,
                            ConvDims d, int bn, int mtiles,
                            hipStream_t stream);

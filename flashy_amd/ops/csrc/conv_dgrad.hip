@@ -204,23 +204,104 @@ k_conv_dgrad(const uint16_t* __restrict__ dout, const uint16_t* __restrict__ w_r
             }
 }
 
-extern "C" int launch_conv_dgrad_s2(const void* dout, const void* w_rsck,
-                                    void* dx, ConvDims d, hipStream_t stream);
+extern "C" void launch_conv_dgrad_s2(const void* dout, const void* w_rsck,
+                                     void* dx, ConvDims d, int bm,
+                                     hipStream_t stream);
+
+static void launch_conv_dgrad_generic(const void* dout, const void* w_rsck,
+                                      void* dx, ConvDims d,
+                                      hipStream_t stream);
+
+// Stride-2 plan: which form computes dx without zero-filled MFMA work, and
+// its tile (BN for the 8-wave forms, BM for the 4-wave parity kernel).
+// ops.conv_dgrad asks it before it considers split-K; thresholds from
+// profiles/r05a_dgrad_s2_sweep.txt.
+extern "C" int conv_dgrad_s2_plan(ConvDims d, int* tile_out) {
+    *tile_out = 0;
+    if (d.stride != 2 || d.C % 64 || d.K % 64) return DGRAD_S2_NONE;
+    const int64_t Mc = (int64_t)d.N * ((d.H + 1) / 2) * ((d.W + 1) / 2);
+    const int ktiles = d.C / CONV_BN;
+    const bool par4_32 = (Mc + 31) / 32 * ktiles * 4 >= 104;
+    if (d.R == 1 && d.S == 1) {
+        if (conv_dgrad8_s2_plan(d, tile_out)) return DGRAD_S2_SCAT2;
+        // below SCAT2's floor: where the generic 8-wave kernel has its grid
+        // it is write-bound already (9.2 us at 64 <- 128, every other form
+        // slower); where it has not, 32-row parity tiles — class 0 is the
+        // quarter GEMM, the three tapless classes store zeros
+        int bn8;
+        *tile_out = 0;
+        if (conv_dgrad8_plan(d, &bn8) || !par4_32) return DGRAD_S2_NONE;
+        *tile_out = 32;
+        return DGRAD_S2_PAR4;
+    }
+    // the four classes run 4:2:2:1 stages (3x3), so blocks of the short
+    // classes retire early: the 8-wave form needs its floor in class blocks
+    const int mt8 = conv8_disabled() ? 0 : conv_dgrad8_par2_mtiles(d);
+    if (mt8 && pick_bn8(mt8 * 4, d.C, kPar8Floor, tile_out))
+        return DGRAD_S2_PAR8;
+    if (!par4_32) return DGRAD_S2_NONE;   // generic, split-K allowed
+    // under that floor 32-row tiles beat 64 and 128 at every measured shape
+    // (most blocks); 128 / 64 are for the 8-wave family switched off
+    *tile_out = 32;
+    if (conv8_disabled())
+        for (int cand : {128, 64})
+            if ((Mc + cand - 1) / cand * ktiles * 4 >= 208) {
+                *tile_out = cand;
+                break;
+            }
+    return DGRAD_S2_PAR4;
+}
+
+// One stride-2 form, named by the caller: the plan's choice in
+// launch_conv_dgrad, any applicable one from the tests and
+// scripts/dgrad_s2_sweep.py.  Returns 0 when the form cannot run the shape.
+extern "C" int launch_conv_dgrad_s2_form(const void* dout, const void* w_rsck,
+                                         void* dx, ConvDims d, int form,
+                                         int tile, hipStream_t stream) {
+    if (form == DGRAD_S2_NONE) {   // the zero-filled kernels, single pass
+        launch_conv_dgrad_generic(dout, w_rsck, dx, d, stream);
+        return 1;
+    }
+    if (d.stride != 2 || d.C % 64 || d.K % 64) return 0;
+    if (form == DGRAD_S2_PAR8) {
+        const int mt = conv_dgrad8_par2_mtiles(d);
+        if (!mt || (tile != 64 && tile != 128) || d.C % tile) return 0;
+        launch_conv_dgrad8_par2(dout, w_rsck, dx, d, tile, mt, stream);
+        return 1;
+    }
+    if (form == DGRAD_S2_PAR4) {
+        if (tile != 32 && tile != 64 && tile != 128) return 0;
+        launch_conv_dgrad_s2(dout, w_rsck, dx, d, tile, stream);
+        return 1;
+    }
+    if (form == DGRAD_S2_SCAT2) {
+        const int mt = conv_dgrad8_s2_mtiles(d);
+        if (!mt || (tile != 64 && tile != 128) || d.C % tile) return 0;
+        launch_conv_dgrad8_s2(dout, w_rsck, dx, d, tile, mt, stream);
+        return 1;
+    }
+    return 0;
+}
 
 extern "C" void launch_conv_dgrad(const void* dout, const void* w_rsck,
                                   void* dx, ConvDims d, hipStream_t stream) {
+    if (d.stride == 2) {   // a form without zero-filled MFMA work
+        int tile;
+        const int form = conv_dgrad_s2_plan(d, &tile);
+        if (form && launch_conv_dgrad_s2_form(dout, w_rsck, dx, d, form, tile,
+                                              stream))
+            return;
+    }
+    launch_conv_dgrad_generic(dout, w_rsck, dx, d, stream);
+}
+
+static void launch_conv_dgrad_generic(const void* dout, const void* w_rsck,
+                                      void* dx, ConvDims d,
+                                      hipStream_t stream) {
     const int64_t M = (int64_t)d.N * d.H * d.W;
     auto dd = (const uint16_t*)dout;
     auto ww = (const uint16_t*)w_rsck;
     auto xx = (uint16_t*)dx;
-    if (d.stride == 2) {
-        int bn8;   // 1x1 s2: quarter-size GEMM + sibling zero scatter
-        const int mt8 = conv_dgrad8_s2_plan(d, &bn8);
-        if (mt8) {
-            launch_conv_dgrad8_s2(dout, w_rsck, dx, d, bn8, mt8, stream);
-            return;
-        }
-    }
     if (d.R == 1 && d.S == 1 && d.stride == 1 && d.pad == 0 && d.K == 64) {
         // single-stage 1x1 dgrad = the fwd m-loop GEMM with remapped dims:
         // A = dy [M][64], B = w_rsck [C][64] (same [col][red] addressing
@@ -236,9 +317,6 @@ extern "C" void launch_conv_dgrad(const void* dout, const void* w_rsck,
             return;
         }
     }
-    if (d.stride == 2 &&
-        launch_conv_dgrad_s2(dout, w_rsck, dx, d, stream))
-        return;  // parity-class form (no zero-filled MFMA work)
     {
         int bn8;
         const int mt8 = conv_dgrad8_plan(d, &bn8);
@@ -537,28 +615,20 @@ k_conv_dgrad_s2(const uint16_t* __restrict__ dout,
             }
 }
 
-extern "C" int launch_conv_dgrad_s2(const void* dout, const void* w_rsck,
-                                    void* dx, ConvDims d, hipStream_t stream) {
-    if (d.stride != 2) return 0;
-    if (d.R == 1 && d.S == 1) return 0;  // 1x1: the generic kernel is faster
+extern "C" void launch_conv_dgrad_s2(const void* dout, const void* w_rsck,
+                                     void* dx, ConvDims d, int bm,
+                                     hipStream_t stream) {
     // class extents (max over classes) for grid sizing
     const int Hc = (d.H + 1) / 2;
     const int Wc = (d.W + 1) / 2;
     const int64_t Mc = (int64_t)d.N * Hc * Wc;
-    const int ktiles = d.C / CONV_BN;
-    int bm = 32;
-    for (int cand : {128, 64}) {
-        if ((Mc + cand - 1) / cand * ktiles * 4 >= 208) { bm = cand; break; }
-    }
-    if ((Mc + 31) / 32 * ktiles * 4 < 104) return 0;  // too small: caller falls back
-    dim3 grid((unsigned)((Mc + bm - 1) / bm), (unsigned)ktiles, 4);
+    dim3 grid((unsigned)((Mc + bm - 1) / bm), (unsigned)(d.C / CONV_BN), 4);
     auto dd = (const uint16_t*)dout;
     auto ww = (const uint16_t*)w_rsck;
     auto xx = (uint16_t*)dx;
     if (bm == 128) k_conv_dgrad_s2<128><<<grid, CONV_THREADS, 0, stream>>>(dd, ww, xx, d);
     else if (bm == 64) k_conv_dgrad_s2<64><<<grid, CONV_THREADS, 0, stream>>>(dd, ww, xx, d);
     else k_conv_dgrad_s2<32><<<grid, CONV_THREADS, 0, stream>>>(dd, ww, xx, d);
-    return 1;
 }
 
 #include <cstdlib>

@@ -20,7 +20,19 @@
 // even (hi, wi), so A rows are the OUTPUT pixels read linearly from dy and
 // the epilogue scatters each result to (2ho, 2wo) while writing the three
 // odd-position siblings as zeros (no zero-filled MFMA work, no memset pass).
-template <int BN, bool S1, bool SCAT2 = false, bool SPLITK = false>
+//
+// PAR2: stride-2 dgrad by parity class — grid.z enumerates the four
+// (ph, pw) = ((hi+pad)%2, (wi+pad)%2) classes of input pixels.  Only taps
+// r = ph + 2r', s = pw + 2s' reach a class, with ho = (hi+pad-ph)/2 - r', so
+// within a class the problem is a stride-1 gather over the dy grid with an
+// Rp x Sp tap subset (3x3 pad 1: 4 / 2 / 2 / 1 taps for z = 0..3, so the
+// longest class is dispatched first): A rows are the class's pixels, the
+// tap walk runs over (r', s', k), B reads the (ph+2r', pw+2s') slab of the
+// RSCK weights and the epilogue writes every other pixel.  A class no tap
+// reaches (R or S == 1) runs no stage and stores zeros.  Instantiated with
+// S1 = true (ho = hb - r' needs no division).
+template <int BN, bool S1, bool SCAT2 = false, bool SPLITK = false,
+          bool PAR2 = false>
 __global__ void __launch_bounds__(512, 2)
 k_conv_dgrad8(const uint16_t* __restrict__ dout,
               const uint16_t* __restrict__ w_rsck,
@@ -39,9 +51,19 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
     constexpr int BUFS = BN == 64 ? 4 : 3;
     constexpr int DEPTH = BUFS - 2;
 
-    const int rsk = d.R * d.S * d.K;
+    // PAR2 class geometry: first input coordinate (a0, b0), extents (Hc, Wc)
+    // and tap counts (Rt, St) of this block's class; else the full filter
+    const int ph = PAR2 ? (int)(blockIdx.z >> 1) : 0;
+    const int pw = PAR2 ? (int)(blockIdx.z & 1) : 0;
+    const int a0 = PAR2 ? (ph + d.pad) & 1 : 0;
+    const int b0 = PAR2 ? (pw + d.pad) & 1 : 0;
+    const int Hc = PAR2 ? (a0 < d.H ? (d.H - a0 + 1) >> 1 : 0) : d.H;
+    const int Wc = PAR2 ? (b0 < d.W ? (d.W - b0 + 1) >> 1 : 0) : d.W;
+    const int Rt = PAR2 ? (ph < d.R ? (d.R - ph + 1) >> 1 : 0) : d.R;
+    const int St = PAR2 ? (pw < d.S ? (d.S - pw + 1) >> 1 : 0) : d.S;
+    const int rsk = Rt * St * d.K;
     const int64_t M = SCAT2 ? (int64_t)d.N * d.Ho * d.Wo
-                            : (int64_t)d.N * d.H * d.W;
+                            : (int64_t)d.N * Hc * Wc;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid_u = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -53,6 +75,7 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
         bx = (bx & 7) * (gridDim.x >> 3) + (bx >> 3);
     const int64_t m0 = (int64_t)bx * BM;
     const int col0 = blockIdx.y * BN;
+    if (PAR2 && m0 >= M) return;   // grid.x is sized by the largest class
 
     __shared__ uint16_t lds[BUFS * BUF_ELEMS];
 
@@ -71,17 +94,22 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
         if (SCAT2) {
             a_n[g] = m < M ? m : -1;   // linear dy row (1x1 over out grid)
         } else if (m < M) {
-            const int hw = d.H * d.W;
+            const int hw = Hc * Wc;
             a_n[g] = m / hw;
             const int rem = (int)(m % hw);
-            a_hi[g] = rem / d.W + d.pad;
-            a_wi[g] = rem % d.W + d.pad;
+            if (PAR2) {   // (hb, wb) = (ho, wo) of tap r' = s' = 0
+                a_hi[g] = (a0 + 2 * (rem / Wc) + d.pad - ph) >> 1;
+                a_wi[g] = (b0 + 2 * (rem % Wc) + d.pad - pw) >> 1;
+            } else {
+                a_hi[g] = rem / d.W + d.pad;
+                a_wi[g] = rem % d.W + d.pad;
+            }
         } else {
             a_n[g] = -1;
         }
         const int kk = (SPLITK ? blockIdx.z * spz * 64 : 0) + kc_s * 8;
-        a_r[g] = kk / (d.S * d.K);
-        const int sk = kk - a_r[g] * d.S * d.K;
+        a_r[g] = PAR2 && St == 0 ? 0 : kk / (St * d.K);
+        const int sk = kk - a_r[g] * St * d.K;
         a_s[g] = sk / d.K;
         a_k[g] = sk - a_s[g] * d.K;
     }
@@ -94,8 +122,8 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
         const int kc_s = (chunk & 7) ^ (col & 7);
         b_col[g] = col0 + col;
         const int kk = (SPLITK ? blockIdx.z * spz * 64 : 0) + kc_s * 8;
-        b_r[g] = kk / (d.S * d.K);
-        const int sk = kk - b_r[g] * d.S * d.K;
+        b_r[g] = PAR2 && St == 0 ? 0 : kk / (St * d.K);
+        const int sk = kk - b_r[g] * St * d.K;
         b_s[g] = sk / d.K;
         b_k[g] = sk - b_s[g] * d.K;
     }
@@ -109,7 +137,7 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
                 if (a_n[g] >= 0)
                     voff = (unsigned)((a_n[g] * d.K + a_k[g]) * 2);
                 a_k[g] += BK;   // 1x1: k never wraps within rsk
-            } else if (a_n[g] >= 0 && a_r[g] < d.R) {
+            } else if (a_n[g] >= 0 && a_r[g] < Rt) {
                 const int hnum = a_hi[g] - a_r[g];   // = ho * stride
                 const int wnum = a_wi[g] - a_s[g];
                 const int ho = S1 ? hnum : hnum / d.stride;
@@ -124,7 +152,7 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
                 int k = a_k[g] + BK;
                 while (k >= d.K) {
                     k -= d.K;
-                    if (++a_s[g] == d.S) { a_s[g] = 0; ++a_r[g]; }
+                    if (++a_s[g] == St) { a_s[g] = 0; ++a_r[g]; }
                 }
                 a_k[g] = k;
             }
@@ -137,13 +165,15 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
         uint16_t* bbase = base + A_ELEMS;
 #pragma unroll
         for (int g = 0; g < NF; ++g) {
+            const int br = PAR2 ? ph + 2 * b_r[g] : b_r[g];
+            const int bs = PAR2 ? pw + 2 * b_s[g] : b_s[g];
             const int64_t off =
-                (((int64_t)b_r[g] * d.S + b_s[g]) * d.C + b_col[g]) *
+                (((int64_t)br * d.S + bs) * d.C + b_col[g]) *
                     (int64_t)d.K + b_k[g];
             int k = b_k[g] + BK;
             while (k >= d.K) {
                 k -= d.K;
-                if (++b_s[g] == d.S) { b_s[g] = 0; ++b_r[g]; }
+                if (++b_s[g] == St) { b_s[g] = 0; ++b_r[g]; }
             }
             b_k[g] = k;
             __builtin_amdgcn_global_load_lds(
@@ -201,22 +231,25 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
         }
     };
 
-    for (int p = 0; p < DEPTH && p < n_stages; ++p)
-        issue_stage(p % BUFS);
-    for (int i = 0; i + DEPTH < n_stages; ++i) {
-        issue_stage((i + DEPTH) % BUFS);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(DEPTH * G) : "memory");
+    // a PAR2 class without taps has no stage to run: acc stays zero
+    if (!PAR2 || n_stages > 0) {
+        for (int p = 0; p < DEPTH && p < n_stages; ++p)
+            issue_stage(p % BUFS);
+        for (int i = 0; i + DEPTH < n_stages; ++i) {
+            issue_stage((i + DEPTH) % BUFS);
+            asm volatile("s_waitcnt vmcnt(%0)" ::"i"(DEPTH * G) : "memory");
+            __builtin_amdgcn_s_barrier();
+            compute_stage(i % BUFS);
+        }
+        if (DEPTH == 2 && n_stages >= 2) {   // tail with one stage in flight
+            asm volatile("s_waitcnt vmcnt(%0)" ::"i"(G) : "memory");
+            __builtin_amdgcn_s_barrier();
+            compute_stage((n_stages - 2) % BUFS);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        compute_stage(i % BUFS);
+        compute_stage((n_stages - 1) % BUFS);
     }
-    if (DEPTH == 2 && n_stages >= 2) {   // tail with one stage in flight
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(G) : "memory");
-        __builtin_amdgcn_s_barrier();
-        compute_stage((n_stages - 2) % BUFS);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    compute_stage((n_stages - 1) % BUFS);
 
     const int64_t out_row0 = m0 + wave_m * 128 + (lane & 15);
     const int out_col0 = col0 + wave_n * (BN / 4) + (lane >> 4) * 4;
@@ -247,6 +280,12 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
                 const int ho = (int)((row / d.Wo) % d.Ho);
                 const int64_t n = row / ((int64_t)d.Ho * d.Wo);
                 obase = ((n * d.H + 2 * ho) * d.W + 2 * wo) * (int64_t)d.C;
+            } else if (PAR2) {   // class row -> every other pixel of dx
+                const int wc = (int)(row % Wc);
+                const int hc = (int)((row / Wc) % Hc);
+                const int64_t n = row / ((int64_t)Hc * Wc);
+                obase = ((n * d.H + a0 + 2 * hc) * d.W + b0 + 2 * wc) *
+                        (int64_t)d.C;
             } else {
                 obase = row * d.C;
             }
@@ -280,33 +319,63 @@ extern "C" int conv_dgrad8_plan(ConvDims d, int* bn_out) {
     return pick_bn8(mtiles, d.C, 160, bn_out) ? mtiles : 0;
 }
 
-// 1x1 stride-2 plan: quarter-size GEMM over the output grid (SCAT2)
-extern "C" int conv_dgrad8_s2_plan(ConvDims d, int* bn_out) {
+// SCAT2 grid.x (0 = the shape cannot take it): 1x1 stride 2, even H/W
+extern "C" int conv_dgrad8_s2_mtiles(ConvDims d) {
     if (d.R != 1 || d.S != 1 || d.stride != 2) return 0;
     if (d.C % 64 || d.K % 64) return 0;
     const int64_t Mq = (int64_t)d.N * d.Ho * d.Wo;
     const int64_t dout_elems = Mq * d.K;
     if (dout_elems * 2 >= (int64_t)kOobSentinel) return 0;
     if (d.W % 2 || d.H % 2) return 0;   // sibling zero-stores assume even
-    const int mtiles = (int)((Mq + 255) / 256);
-    return pick_bn8(mtiles, d.C, 104, bn_out) ? mtiles : 0;
+    return (int)((Mq + 255) / 256);
 }
 
-// The three launchers differ only in SCAT2 / SPLITK; S1 follows the stride
-// (SCAT2 reads dy linearly and ignores it).
-template <bool SCAT2_LAUNCH, bool SPLITK>
+// 1x1 stride-2 plan: quarter-size GEMM over the output grid (SCAT2), from
+// 104 blocks; BN=128 only from 160 (at 104 blocks it measured 48.0 us
+// against 32.6 us for BN=64 on 14x14x1024 <- 2048, profiles/r05a)
+extern "C" int conv_dgrad8_s2_plan(ConvDims d, int* bn_out) {
+    const int mtiles = conv_dgrad8_s2_mtiles(d);
+    if (!mtiles) return 0;
+    if (d.C % 128 == 0 && (int64_t)mtiles * (d.C / 128) >= 160) {
+        *bn_out = 128;
+        return mtiles;
+    }
+    if ((int64_t)mtiles * (d.C / 64) < 104) return 0;
+    *bn_out = 64;
+    return mtiles;
+}
+
+// The launchers differ only in SCAT2 / SPLITK / PAR2; S1 follows the stride
+// (SCAT2 reads dy linearly and ignores it, PAR2 walks its class at stride 1).
+template <bool SCAT2_LAUNCH, bool SPLITK, bool PAR2 = false>
 static void launch_dgrad8(const void* dout, const void* w_rsck, void* out,
                           ConvDims d, int bn, int mtiles, int spz, int zeff,
                           hipStream_t stream) {
     dim3 grid((unsigned)mtiles, (unsigned)(d.C / bn), (unsigned)zeff);
     const unsigned db = (unsigned)((int64_t)d.N * d.Ho * d.Wo * d.K * 2);
-    dispatch8(bn, d.stride == 1, [&](auto BN, auto S1) {
-        constexpr bool s1 = !SCAT2_LAUNCH && decltype(S1)::value;
-        k_conv_dgrad8<decltype(BN)::value, s1, SCAT2_LAUNCH, SPLITK>
+    dispatch8(bn, PAR2 || d.stride == 1, [&](auto BN, auto S1) {
+        constexpr bool s1 = PAR2 || (!SCAT2_LAUNCH && decltype(S1)::value);
+        k_conv_dgrad8<decltype(BN)::value, s1, SCAT2_LAUNCH, SPLITK, PAR2>
             <<<grid, 512, 0, stream>>>((const uint16_t*)dout,
                                        (const uint16_t*)w_rsck,
                                        (uint16_t*)out, d, db, spz);
     });
+}
+
+// 8-wave parity-class grid.x: 256-row tiles of the largest class
+extern "C" int conv_dgrad8_par2_mtiles(ConvDims d) {
+    if (d.stride != 2 || d.C % 64 || d.K % 64) return 0;
+    const int64_t dout_elems = (int64_t)d.N * d.Ho * d.Wo * d.K;
+    if (dout_elems * 2 >= (int64_t)kOobSentinel) return 0;
+    const int64_t Mc = (int64_t)d.N * ((d.H + 1) / 2) * ((d.W + 1) / 2);
+    return (int)((Mc + 255) / 256);
+}
+
+extern "C" void launch_conv_dgrad8_par2(const void* dout, const void* w_rsck,
+                                        void* dx, ConvDims d, int bn,
+                                        int mtiles, hipStream_t stream) {
+    launch_dgrad8<false, false, true>(dout, w_rsck, dx, d, bn, mtiles, 0, 4,
+                                      stream);
 }
 
 extern "C" void launch_conv_dgrad8_s2(const void* dout, const void* w_rsck,

@@ -282,6 +282,28 @@ PYBIND11_MODULE(_hip_ops, m) {
                                 as_stream(stream));
               check_last();
           });
+    // stride-2 dgrad: the plan's (form, tile), and one form launched by name
+    // (tests and scripts/dgrad_s2_sweep.py; form 0 = the generic kernels)
+    m.def("conv_dgrad_s2_plan",
+          [](int N, int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad) {
+              int tile = 0;
+              const int form = conv_dgrad_s2_plan(
+                  make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad), &tile);
+              return py::make_tuple(form, tile);
+          });
+    m.def("conv_dgrad_s2_form",
+          [](uintptr_t dout, uintptr_t w_rsck, uintptr_t dx, int N, int H,
+             int W, int C, int K, int R, int S, int Ho, int Wo, int stride,
+             int pad, int form, int tile, uintptr_t stream) {
+              if (!launch_conv_dgrad_s2_form(
+                      (const void*)dout, (const void*)w_rsck, (void*)dx,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      form, tile, as_stream(stream)))
+                  throw std::invalid_argument(
+                      "conv_dgrad_s2_form: form/tile cannot run this shape");
+              check_last();
+          });
     m.def("conv_fwd_splitk",
           [](uintptr_t x, uintptr_t w, uintptr_t ws, int N, int H, int W,
              int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
