@@ -173,6 +173,10 @@ class _BnFn(torch.autograd.Function):
         N, H, W, C = x.shape
         M = N * H * W
         y = torch.empty_like(x)
+        # small-M layers: one kernel forward, one backward (the plan lives
+        # in batchnorm.hip); eval mode always keeps the separate kernels
+        fwd_form, bwd_form = ops.bn_small_plan(M, C) if module.training \
+            else ("chain", "chain")
         if module.training:
             fused = getattr(x, "_bn_stats", None)
             if fused is not None:   # producing conv already emitted partials
@@ -183,18 +187,27 @@ class _BnFn(torch.autograd.Function):
                                        device=x.device)
                 ops.bn_stats(x, partials, M, C, msplit)
             work = torch.empty(4 * C, dtype=torch.float32, device=x.device)
-            ops.bn_finalize(partials, msplit, gamma, beta, module.running_mean,
-                            module.running_var, work, M, C, module.eps,
-                            module.momentum, update_running=True)
+            if fwd_form == "small":
+                ops.bn_fwd_small(partials, msplit, gamma, beta,
+                                 module.running_mean, module.running_var, work,
+                                 x, res, y, M, C, module.eps, module.momentum,
+                                 True, relu, slope)
+            else:
+                ops.bn_finalize(partials, msplit, gamma, beta,
+                                module.running_mean, module.running_var, work,
+                                M, C, module.eps, module.momentum,
+                                update_running=True)
         else:
             invstd = torch.rsqrt(module.running_var + module.eps)
             scale = gamma.detach() * invstd
             shift = beta.detach() - module.running_mean * scale
             work = torch.cat([module.running_mean, invstd, scale, shift])
-        ops.bn_apply(x, res, y, work, M, C, relu, slope)
+        if fwd_form != "small":
+            ops.bn_apply(x, res, y, work, M, C, relu, slope)
         ctx.save_for_backward(x, y, work)
         ctx.relu = relu
         ctx.slope = slope
+        ctx.bwd_form = bwd_form   # "chain" in eval mode
         ctx.has_res = res is not None
         ctx.refs = (gamma, beta)
         return y
@@ -206,24 +219,31 @@ class _BnFn(torch.autograd.Function):
         N, H, W, C = x.shape
         M = N * H * W
         dy = dy.contiguous()
-        msplit = ops.bn_msplit(M, C)
-        partials = torch.empty(msplit * 2 * C, dtype=torch.float32,
-                               device=x.device)
-        bsums = torch.empty(2 * C, dtype=torch.float32, device=x.device)
-        dz = torch.empty_like(dy)
-        ops.bn_bwd_reduce(dy, y, x, work, dz, partials, M, C, msplit,
-                          ctx.relu, ctx.slope)
-        # bn_bwd_grads also produces bsums (needed for dx), so the kernel
-        # always runs; frozen gamma/beta just accumulate into a discarded
-        # temp instead of param.grad (never pollute frozen params' grads).
+        # the sums are needed for dx, so the grads step always runs; frozen
+        # gamma/beta just accumulate into a discarded temp instead of
+        # param.grad (never pollute frozen params' grads).
         need_g, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         dgamma, g_direct = _grad_target(gamma) if need_g \
             else (torch.empty_like(gamma), True)
         dbeta, b_direct = _grad_target(beta) if need_b \
             else (torch.empty_like(beta), True)
-        ops.bn_bwd_grads(partials, msplit, bsums, dgamma, dbeta, C)
         dx = torch.empty_like(x)
-        ops.bn_bwd_apply(dz, x, work, bsums, dx, M, C)
+        if ctx.bwd_form != "chain":
+            # dz is the residual branch's gradient: written only if one reads it
+            dz = torch.empty_like(dy) if ctx.has_res else None
+            ops.bn_bwd_small(dy, y, x, work, dz, dgamma, dbeta, dx, M, C,
+                             ctx.relu, ctx.slope, write_dz=ctx.has_res,
+                             form=ctx.bwd_form)
+        else:
+            msplit = ops.bn_msplit(M, C)
+            partials = torch.empty(msplit * 2 * C, dtype=torch.float32,
+                                   device=x.device)
+            bsums = torch.empty(2 * C, dtype=torch.float32, device=x.device)
+            dz = torch.empty_like(dy)
+            ops.bn_bwd_reduce(dy, y, x, work, dz, partials, M, C, msplit,
+                              ctx.relu, ctx.slope)
+            ops.bn_bwd_grads(partials, msplit, bsums, dgamma, dbeta, C)
+            ops.bn_bwd_apply(dz, x, work, bsums, dx, M, C)
         return (dx,
                 dgamma if need_g and not g_direct else None,
                 dbeta if need_b and not b_direct else None,

@@ -871,6 +871,55 @@ def bn_bwd_apply(dz, x, work, bsums, dx, M: int, C: int) -> None:
                            bsums.data_ptr(), dx.data_ptr(), M, C, _stream())
 
 
+BN_BWD_SMALL_FORMS = {"chain": 0, "regs8": 1}
+
+
+def bn_small_plan(M: int, C: int) -> tp.Tuple[str, str]:
+    """(forward form, backward form) the plan picks for a training BatchNorm
+    over ``[M, C]``: forward "small" (finalize + apply in one kernel) or
+    "chain"; backward one of :data:`BN_BWD_SMALL_FORMS` (reduce + grads +
+    apply in one kernel, 8 channels per block, its rows kept in registers) or
+    "chain" (the separate kernels)."""
+    fwd, bwd = require().bn_small_plan(M, C)
+    names = {v: k for k, v in BN_BWD_SMALL_FORMS.items()}
+    return ("small" if fwd else "chain"), names[bwd]
+
+
+def bn_fwd_small(partials, msplit: int, gamma, beta, rmean, rvar, work, x,
+                 res, y, M: int, C: int, eps: float, momentum: float,
+                 update_running: bool, relu: bool, slope: float = 0.0) -> None:
+    """:func:`bn_finalize` + :func:`bn_apply` in one launch, whatever the plan
+    says (tests and scripts/bn_small_sweep.py); bitwise the chain's ``y``,
+    ``work`` and running statistics.  Raises where it cannot run the shape."""
+    assert x.is_contiguous() and y.is_contiguous() and x.numel() == M * C
+    assert res is None or res.is_contiguous()
+    require().bn_fwd_small(
+        partials.data_ptr(), msplit, gamma.data_ptr(), beta.data_ptr(),
+        rmean.data_ptr(), rvar.data_ptr(), work.data_ptr(), x.data_ptr(),
+        res.data_ptr() if res is not None else 0, y.data_ptr(), M, C, eps,
+        momentum, update_running, relu, slope, 1, _stream())
+
+
+def bn_bwd_small(dy, y, x, work, dz, dgamma, dbeta, dx, M: int, C: int,
+                 relu: bool, slope: float = 0.0, write_dz: bool = True,
+                 form: str = "regs8") -> None:
+    """:func:`bn_bwd_reduce` + :func:`bn_bwd_grads` + :func:`bn_bwd_apply` in
+    one launch through the named form, whatever the plan says.  ``dgamma`` /
+    ``dbeta`` are accumulated (+=); ``dz`` is written only with ``write_dz``
+    (and may be None without it).
+    Raises where the form cannot run the shape."""
+    assert all(t.is_contiguous() for t in (dy, y, x, dx))
+    assert x.numel() == M * C
+    assert dz.is_contiguous() if write_dz else True
+    if form == "chain":
+        raise ValueError("bn_bwd_small: 'chain' is not a single-kernel form")
+    require().bn_bwd_small(
+        dy.data_ptr(), y.data_ptr(), x.data_ptr(), work.data_ptr(),
+        dz.data_ptr() if dz is not None else 0, dgamma.data_ptr(),
+        dbeta.data_ptr(), dx.data_ptr(),
+        M, C, relu, slope, write_dz, BN_BWD_SMALL_FORMS[form], _stream())
+
+
 # ---------------------------------------------------------------------------
 # loss kernels (fused forward+input-grad; see flashy_amd/functional.py)
 # ---------------------------------------------------------------------------

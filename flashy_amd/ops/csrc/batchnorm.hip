@@ -114,6 +114,34 @@ __device__ __forceinline__ void combine_partials8(
 }
 
 // work[0..C) = mean, [C..2C) = invstd, [2C..3C) = scale, [3C..4C) = shift
+// One channel's finalize, run by the 8 writer threads of a combine block;
+// shared by k_bn_finalize and k_bn_fwd_small, which must agree bit for bit.
+__device__ __forceinline__ void bn_finalize_channel(
+        float s, float s2, int c,
+        const float* __restrict__ gamma, const float* __restrict__ beta,
+        float* __restrict__ running_mean, float* __restrict__ running_var,
+        float* __restrict__ work, int64_t M, int C,
+        float eps, float momentum, int update_running,
+        float* scale_out, float* shift_out) {
+    const float mean = s / (float)M;
+    float var = s2 / (float)M - mean * mean;
+    var = fmaxf(var, 0.f);
+    const float invstd = rsqrtf(var + eps);
+    const float scale = gamma[c] * invstd;
+    const float shift = beta[c] - mean * scale;
+    work[c] = mean;
+    work[C + c] = invstd;
+    work[2 * C + c] = scale;
+    work[3 * C + c] = shift;
+    if (update_running) {
+        running_mean[c] += momentum * (mean - running_mean[c]);
+        const float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
+        running_var[c] += momentum * (unbiased - running_var[c]);
+    }
+    *scale_out = scale;
+    *shift_out = shift;
+}
+
 __global__ void __launch_bounds__(256)
 k_bn_finalize(const float* __restrict__ partials, int msplit,
               const float* __restrict__ gamma,
@@ -125,21 +153,10 @@ k_bn_finalize(const float* __restrict__ partials, int msplit,
     float s, s2;
     combine_partials8(partials, msplit, C, &s, &s2);
     if (threadIdx.x >= 8) return;
-    const int c = blockIdx.x * 8 + threadIdx.x;
-    const float mean = s / (float)M;
-    float var = s2 / (float)M - mean * mean;
-    var = fmaxf(var, 0.f);
-    const float invstd = rsqrtf(var + eps);
-    const float scale = gamma[c] * invstd;
-    work[c] = mean;
-    work[C + c] = invstd;
-    work[2 * C + c] = scale;
-    work[3 * C + c] = beta[c] - mean * scale;
-    if (update_running) {
-        running_mean[c] += momentum * (mean - running_mean[c]);
-        const float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
-        running_var[c] += momentum * (unbiased - running_var[c]);
-    }
+    float scale, shift;
+    bn_finalize_channel(s, s2, blockIdx.x * 8 + threadIdx.x, gamma, beta,
+                        running_mean, running_var, work, M, C, eps, momentum,
+                        update_running, &scale, &shift);
 }
 
 // ---------------------------------------------------------------------------
@@ -176,6 +193,27 @@ k_bn_apply(const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
     }
 }
 
+// One output element of the forward apply / of the backward dx; shared by the
+// channel-resident kernels below and the single-kernel small-M forms.
+template <bool RELU, bool RES>
+__device__ __forceinline__ uint16_t bn_apply_elem(uint16_t x, uint16_t r,
+                                                  float sc, float sh,
+                                                  float slope) {
+    float v = fmaf(bf16_to_f32(x), sc, sh);
+    if (RES) v += bf16_to_f32(r);
+    if (RELU) v = v > 0.f ? v : slope * v;
+    return f32_to_bf16(v);
+}
+
+// b0 = sum(dz)/M, b1 = sum(dz*xhat)/M
+__device__ __forceinline__ uint16_t bn_bwd_dx_elem(uint16_t dz, uint16_t x,
+                                                   float mn, float is, float sc,
+                                                   float b0, float b1) {
+    const float xhat = (bf16_to_f32(x) - mn) * is;
+    const float g = bf16_to_f32(dz);
+    return f32_to_bf16(sc * (g - b0 - xhat * b1));
+}
+
 // Channel-resident variant for C % 64 == 0 (every trunk BN): thread owns a
 // fixed 8-channel group, coefficients load ONCE into registers, the loop is
 // pure 16B streaming over m — no per-iteration int64 div/mod (the generic
@@ -202,12 +240,10 @@ k_bn_apply_c64(const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
         if (RES) rv = *reinterpret_cast<const short8*>(res + off);
         short8 out;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float v = fmaf(bf16_to_f32(((const uint16_t*)&xv)[j]), sc[j], sh[j]);
-            if (RES) v += bf16_to_f32(((const uint16_t*)&rv)[j]);
-            if (RELU) v = v > 0.f ? v : slope * v;
-            ((uint16_t*)&out)[j] = f32_to_bf16(v);
-        }
+        for (int j = 0; j < 8; ++j)
+            ((uint16_t*)&out)[j] = bn_apply_elem<RELU, RES>(
+                ((const uint16_t*)&xv)[j], ((const uint16_t*)&rv)[j],
+                sc[j], sh[j], slope);
         *reinterpret_cast<short8*>(y + off) = out;
     }
 }
@@ -239,13 +275,10 @@ k_bn_bwd_apply_c64(const uint16_t* __restrict__ dz,
         short8 xv = *reinterpret_cast<const short8*>(x + off);
         short8 out;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float xhat = (bf16_to_f32(((const uint16_t*)&xv)[j]) - mn[j])
-                               * is[j];
-            const float g = bf16_to_f32(((const uint16_t*)&gz)[j]);
-            ((uint16_t*)&out)[j] =
-                f32_to_bf16(sc[j] * (g - b0[j] - xhat * b1[j]));
-        }
+        for (int j = 0; j < 8; ++j)
+            ((uint16_t*)&out)[j] = bn_bwd_dx_elem(
+                ((const uint16_t*)&gz)[j], ((const uint16_t*)&xv)[j],
+                mn[j], is[j], sc[j], b0[j], b1[j]);
         *reinterpret_cast<short8*>(dx + off) = out;
     }
 }
@@ -376,6 +409,213 @@ k_bn_bwd_apply(const uint16_t* __restrict__ dz, const uint16_t* __restrict__ x,
 }
 
 // ---------------------------------------------------------------------------
+// Small-M single-kernel forms.  BatchNorm is independent per channel, so a
+// block that owns a few channels and walks ALL M rows holds the complete
+// per-channel sums itself: no partials round trip, no second launch.  Grid
+// C/8 (C/4 for the 4-channel backward), 256 threads, thread t takes rows
+// t, t+256, ...  Pays only while M is small (bn_small_plan): the grid is a
+// few dozen blocks, each streaming M rows of 16 B.
+// ---------------------------------------------------------------------------
+
+// fwd: finalize + apply.  The combine and the finalize arithmetic are the
+// chain's own (combine_partials8, bn_finalize_channel), so y, work and the
+// running statistics equal bn_finalize + bn_apply bit for bit.  The first
+// four rows of x (and res) are fetched before the combine, whose latency
+// they hide; M <= 1024 never loads after it.
+template <bool RELU, bool RES>
+__global__ void __launch_bounds__(256)
+k_bn_fwd_small(const float* __restrict__ partials, int msplit,
+               const float* __restrict__ gamma, const float* __restrict__ beta,
+               float* __restrict__ running_mean,
+               float* __restrict__ running_var, float* __restrict__ work,
+               const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
+               uint16_t* __restrict__ y, int64_t M, int C, float eps,
+               float momentum, int update_running, float slope) {
+    const int c0 = blockIdx.x * 8;
+    short8 xv[4] = {}, rv[4] = {};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t m = threadIdx.x + 256 * r;
+        if (m < M) {
+            xv[r] = *reinterpret_cast<const short8*>(x + m * C + c0);
+            if (RES) rv[r] = *reinterpret_cast<const short8*>(res + m * C + c0);
+        }
+    }
+    float s, s2;
+    combine_partials8(partials, msplit, C, &s, &s2);
+    __shared__ float coef[2][8];
+    if (threadIdx.x < 8) {
+        float scale, shift;
+        bn_finalize_channel(s, s2, c0 + threadIdx.x, gamma, beta, running_mean,
+                            running_var, work, M, C, eps, momentum,
+                            update_running, &scale, &shift);
+        coef[0][threadIdx.x] = scale;
+        coef[1][threadIdx.x] = shift;
+    }
+    __syncthreads();
+    float sc[8], sh[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        sc[j] = coef[0][j];
+        sh[j] = coef[1][j];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t m = threadIdx.x + 256 * r;
+        if (m < M) {
+            short8 out;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                ((uint16_t*)&out)[j] = bn_apply_elem<RELU, RES>(
+                    ((const uint16_t*)&xv[r])[j], ((const uint16_t*)&rv[r])[j],
+                    sc[j], sh[j], slope);
+            *reinterpret_cast<short8*>(y + m * C + c0) = out;
+        }
+    }
+    for (int64_t m = threadIdx.x + 1024; m < M; m += 256) {
+        const int64_t off = m * C + c0;
+        const short8 xr = *reinterpret_cast<const short8*>(x + off);
+        short8 rr = {};
+        if (RES) rr = *reinterpret_cast<const short8*>(res + off);
+        short8 out;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            ((uint16_t*)&out)[j] = bn_apply_elem<RELU, RES>(
+                ((const uint16_t*)&xr)[j], ((const uint16_t*)&rr)[j],
+                sc[j], sh[j], slope);
+        *reinterpret_cast<short8*>(y + off) = out;
+    }
+}
+
+template <int CW> struct bn_vec {
+    using type = __attribute__((ext_vector_type(CW))) short;
+};
+
+// One row of backward pass 1: dz = bf16(dy * relu-mask), sums of the
+// unrounded g and g*xhat — the expressions of k_bn_bwd_reduce.
+template <bool RELU, int CW>
+__device__ __forceinline__ void bn_bwd_row(
+        const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
+        const uint16_t* __restrict__ x, int64_t off, const float* mean,
+        const float* invstd, float slope, float* s, float* sx,
+        typename bn_vec<CW>::type* dz_out, typename bn_vec<CW>::type* x_out) {
+    using vec = typename bn_vec<CW>::type;
+    const vec gv = *reinterpret_cast<const vec*>(dy + off);
+    const vec xv = *reinterpret_cast<const vec*>(x + off);
+    vec yv = {};
+    if (RELU) yv = *reinterpret_cast<const vec*>(y + off);
+    vec dzv;
+#pragma unroll
+    for (int j = 0; j < CW; ++j) {
+        float g = bf16_to_f32(((const uint16_t*)&gv)[j]);
+        if (RELU && bf16_to_f32(((const uint16_t*)&yv)[j]) <= 0.f)
+            g *= slope;
+        ((uint16_t*)&dzv)[j] = f32_to_bf16(g);
+        s[j] += g;
+        const float xh = (bf16_to_f32(((const uint16_t*)&xv)[j]) - mean[j]) * invstd[j];
+        sx[j] = fmaf(g, xh, sx[j]);
+    }
+    *dz_out = dzv;
+    *x_out = xv;
+}
+
+// bwd: reduce + grads + apply.  Pass 1 sums g and g*xhat per thread (dz is
+// stored only when WRITE_DZ: it is the residual branch's gradient and has no
+// other reader); the 256 threads' sums fold through LDS in a fixed order (no
+// atomics: bitwise repeatable); dbeta/dgamma += the sums; pass 2 writes dx
+// from the bf16-rounded dz, as the chain's apply reads it.
+// The R rows of a thread (M <= 256*R) stay in registers between the passes;
+// re-reading them in pass 2 instead lost everywhere in the sweep and is gone,
+// as is a 4-channel block (CW stays a parameter; only 8 is instantiated).
+// Blocks are dispatched round-robin over the 8 XCDs, and 64/CW neighbouring
+// channel groups share each 128-byte line of a row: block b takes group
+// (b%8)*(grid/8) + b/8, so the blocks one XCD receives own adjacent groups
+// and its L2 fetches a line once (placement only; any order is correct).
+template <bool RELU, bool WRITE_DZ, int CW, int R>
+__global__ void __launch_bounds__(256)
+k_bn_bwd_small(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
+               const uint16_t* __restrict__ x, const float* __restrict__ work,
+               uint16_t* __restrict__ dz_out, float* __restrict__ dgamma,
+               float* __restrict__ dbeta, uint16_t* __restrict__ dx,
+               int64_t M, int C, float slope) {
+    using vec = typename bn_vec<CW>::type;
+    constexpr int NQ = 128 / CW;      // fold stage 1: row groups per sum kind
+    int grp = blockIdx.x;
+    if (gridDim.x % 8 == 0)
+        grp = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const int c0 = grp * CW;
+    const int t = threadIdx.x;
+    float mean[CW], invstd[CW];
+#pragma unroll
+    for (int j = 0; j < CW; ++j) {
+        mean[j] = work[c0 + j];
+        invstd[j] = work[C + c0 + j];
+    }
+    float s[CW] = {}, sx[CW] = {};
+    vec dzk[R], xk[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int64_t m = t + 256 * r;
+        if (m < M) {
+            const int64_t off = m * C + c0;
+            bn_bwd_row<RELU, CW>(dy, y, x, off, mean, invstd, slope, s, sx,
+                                 &dzk[r], &xk[r]);
+            if (WRITE_DZ) *reinterpret_cast<vec*>(dz_out + off) = dzk[r];
+        }
+    }
+    // fold: red[kind][thread][ch] -> NQ row-group sums per (kind, ch) -> one
+    __shared__ float red[2][256][CW];
+    __shared__ float red2[2][NQ][CW];
+    __shared__ float fin[2][CW];
+#pragma unroll
+    for (int j = 0; j < CW; ++j) {
+        red[0][t][j] = s[j];
+        red[1][t][j] = sx[j];
+    }
+    __syncthreads();
+    {
+        const int kind = t >> 7, q = t & 127;
+        const int k = q / CW, ch = q % CW;
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < 256 / NQ; ++i) acc += red[kind][k + NQ * i][ch];
+        red2[kind][k][ch] = acc;
+    }
+    __syncthreads();
+    if (t < 2 * CW) {
+        const int kind = t / CW, ch = t % CW;
+        float acc = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < NQ; ++k) acc += red2[kind][k][ch];
+        fin[kind][ch] = acc;
+        if (kind == 0) dbeta[c0 + ch] += acc;
+        else dgamma[c0 + ch] += acc;
+    }
+    __syncthreads();
+    const float invM = 1.f / (float)M;
+    float sc[CW], b0[CW], b1[CW];
+#pragma unroll
+    for (int j = 0; j < CW; ++j) {
+        sc[j] = work[2 * (int64_t)C + c0 + j];
+        b0[j] = fin[0][j] * invM;
+        b1[j] = fin[1][j] * invM;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int64_t m = t + 256 * r;
+        if (m < M) {
+            vec out;
+#pragma unroll
+            for (int j = 0; j < CW; ++j)
+                ((uint16_t*)&out)[j] = bn_bwd_dx_elem(
+                    ((const uint16_t*)&dzk[r])[j], ((const uint16_t*)&xk[r])[j],
+                    mean[j], invstd[j], sc[j], b0[j], b1[j]);
+            *reinterpret_cast<vec*>(dx + m * C + c0) = out;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // launchers (msplit chosen by the Python wrapper, shared by both phases)
 // ---------------------------------------------------------------------------
 
@@ -483,4 +723,86 @@ extern "C" void launch_bn_bwd_apply(const void* dz, const void* x,
     k_bn_bwd_apply<<<grid, 256, 0, stream>>>(
         (const uint16_t*)dz, (const uint16_t*)x, (const float*)work,
         (const float*)bsums, (uint16_t*)dx, M, C);
+}
+
+// ---------------------------------------------------------------------------
+// small-M single-kernel forms: plan + launchers
+// ---------------------------------------------------------------------------
+
+// Forward and backward have one form each (1); 0 = the existing chain.
+static inline int bn_bwd_small_rows(int64_t M) {
+    return M <= 1024 ? 4 : M <= 4096 ? 16 : 0;   // rows/thread kept, 0 = none
+}
+
+// The one place that decides which BatchNorms take the single-kernel forms.
+// Thresholds from scripts/bn_small_sweep.py (profiles/README.md, r06a): a
+// block's time grows with M whatever C is.  Backward beats the chain up to
+// M = 1024 (with and without the dz write) and loses at 3136 and 4096;
+// forward, whose block order is tied to combine_partials8, wins at 512 and
+// already loses at 1024.
+extern "C" void bn_small_plan(int64_t M, int C, int* fwd_form, int* bwd_form) {
+    *fwd_form = 0;
+    *bwd_form = 0;
+    if (M < 1 || C < 8 || C % 8) return;
+    if (M <= 512) *fwd_form = 1;
+    if (M <= 1024) *bwd_form = 1;
+}
+
+extern "C" int launch_bn_fwd_small(const void* partials, int msplit,
+                                   const void* gamma, const void* beta,
+                                   void* running_mean, void* running_var,
+                                   void* work, const void* x, const void* res,
+                                   void* y, int64_t M, int C, float eps,
+                                   float momentum, int update_running,
+                                   int relu, float slope, int form,
+                                   hipStream_t stream) {
+    if (form != 1 || M < 1 || C < 8 || C % 8) return 0;
+#define BN_FWD_SMALL(RELU, RES)                                               \
+    k_bn_fwd_small<RELU, RES><<<C / 8, 256, 0, stream>>>(                     \
+        (const float*)partials, msplit, (const float*)gamma,                  \
+        (const float*)beta, (float*)running_mean, (float*)running_var,        \
+        (float*)work, (const uint16_t*)x, (const uint16_t*)res, (uint16_t*)y, \
+        M, C, eps, momentum, update_running, slope)
+    if (relu && res) BN_FWD_SMALL(true, true);
+    else if (relu) BN_FWD_SMALL(true, false);
+    else if (res) BN_FWD_SMALL(false, true);
+    else BN_FWD_SMALL(false, false);
+#undef BN_FWD_SMALL
+    return 1;
+}
+
+template <int CW, int R>
+static void bn_bwd_small_launch(const void* dy, const void* y, const void* x,
+                                const void* work, void* dz, void* dgamma,
+                                void* dbeta, void* dx, int64_t M, int C,
+                                int relu, float slope, int write_dz,
+                                hipStream_t stream) {
+#define BN_BWD_SMALL(RELU, WDZ)                                               \
+    k_bn_bwd_small<RELU, WDZ, CW, R><<<C / CW, 256, 0, stream>>>(             \
+        (const uint16_t*)dy, (const uint16_t*)y, (const uint16_t*)x,          \
+        (const float*)work, (uint16_t*)dz, (float*)dgamma, (float*)dbeta,     \
+        (uint16_t*)dx, M, C, slope)
+    if (relu && write_dz) BN_BWD_SMALL(true, true);
+    else if (relu) BN_BWD_SMALL(true, false);
+    else if (write_dz) BN_BWD_SMALL(false, true);
+    else BN_BWD_SMALL(false, false);
+#undef BN_BWD_SMALL
+}
+
+extern "C" int launch_bn_bwd_small(const void* dy, const void* y,
+                                   const void* x, const void* work, void* dz,
+                                   void* dgamma, void* dbeta, void* dx,
+                                   int64_t M, int C, int relu, float slope,
+                                   int write_dz, int form,
+                                   hipStream_t stream) {
+    if (form != 1 || M < 1 || C < 8 || C % 8) return 0;
+    const int rows = bn_bwd_small_rows(M);
+    if (!rows) return 0;
+#define BN_BWD_GO(CW, R)                                                      \
+    bn_bwd_small_launch<CW, R>(dy, y, x, work, dz, dgamma, dbeta, dx, M, C,   \
+                               relu, slope, write_dz, stream)
+    if (rows == 4) BN_BWD_GO(8, 4);
+    else BN_BWD_GO(8, 16);
+#undef BN_BWD_GO
+    return 1;
 }

@@ -77,6 +77,17 @@ void launch_bn_bwd_grads(const void* partials, int msplit, void* bsums,
 void launch_bn_bwd_apply(const void* dz, const void* x, const void* work,
                          const void* bsums, void* dx, int64_t M, int C,
                          hipStream_t stream);
+void bn_small_plan(int64_t M, int C, int* fwd_form, int* bwd_form);
+int launch_bn_fwd_small(const void* partials, int msplit, const void* gamma,
+                        const void* beta, void* running_mean,
+                        void* running_var, void* work, const void* x,
+                        const void* res, void* y, int64_t M, int C, float eps,
+                        float momentum, int update_running, int relu,
+                        float slope, int form, hipStream_t stream);
+int launch_bn_bwd_small(const void* dy, const void* y, const void* x,
+                        const void* work, void* dz, void* dgamma, void* dbeta,
+                        void* dx, int64_t M, int C, int relu, float slope,
+                        int write_dz, int form, hipStream_t stream);
 void launch_fused_sgd(void* p, const void* g, void* m, void* p_bf16, int64_t n,
                       float lr, float momentum, float wd, float grad_scale,
                       int nesterov, const void* hyper, hipStream_t stream);
@@ -412,6 +423,43 @@ PYBIND11_MODULE(_hip_ops, m) {
               launch_bn_bwd_apply((const void*)dz, (const void*)x,
                                   (const void*)work, (const void*)bsums,
                                   (void*)dx, M, C, as_stream(stream));
+              check_last();
+          });
+    // small-M single-kernel BatchNorm: the plan's (fwd form, bwd form), and
+    // one form launched by name (tests and scripts/bn_small_sweep.py)
+    m.def("bn_small_plan", [](int64_t M, int C) {
+        int fwd = 0, bwd = 0;
+        bn_small_plan(M, C, &fwd, &bwd);
+        return py::make_tuple(fwd, bwd);
+    });
+    m.def("bn_fwd_small",
+          [](uintptr_t partials, int msplit, uintptr_t gamma, uintptr_t beta,
+             uintptr_t rmean, uintptr_t rvar, uintptr_t work, uintptr_t x,
+             uintptr_t res, uintptr_t y, int64_t M, int C, float eps,
+             float momentum, bool update_running, bool relu, float slope,
+             int form, uintptr_t stream) {
+              if (!launch_bn_fwd_small(
+                      (const void*)partials, msplit, (const void*)gamma,
+                      (const void*)beta, (void*)rmean, (void*)rvar,
+                      (void*)work, (const void*)x, (const void*)res, (void*)y,
+                      M, C, eps, momentum, update_running ? 1 : 0,
+                      relu ? 1 : 0, slope, form, as_stream(stream)))
+                  throw std::invalid_argument(
+                      "bn_fwd_small: form cannot run this shape");
+              check_last();
+          });
+    m.def("bn_bwd_small",
+          [](uintptr_t dy, uintptr_t y, uintptr_t x, uintptr_t work,
+             uintptr_t dz, uintptr_t dgamma, uintptr_t dbeta, uintptr_t dx,
+             int64_t M, int C, bool relu, float slope, bool write_dz, int form,
+             uintptr_t stream) {
+              if (!launch_bn_bwd_small(
+                      (const void*)dy, (const void*)y, (const void*)x,
+                      (const void*)work, (void*)dz, (void*)dgamma,
+                      (void*)dbeta, (void*)dx, M, C, relu ? 1 : 0, slope,
+                      write_dz ? 1 : 0, form, as_stream(stream)))
+                  throw std::invalid_argument(
+                      "bn_bwd_small: form cannot run this shape");
               check_last();
           });
 
