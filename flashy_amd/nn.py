@@ -208,6 +208,8 @@ class _BnFn(torch.autograd.Function):
         ctx.relu = relu
         ctx.slope = slope
         ctx.bwd_form = bwd_form   # "chain" in eval mode
+        # with running statistics mean and invstd are constants of x
+        ctx.frozen_stats = not module.training
         ctx.has_res = res is not None
         ctx.refs = (gamma, beta)
         return y
@@ -243,6 +245,12 @@ class _BnFn(torch.autograd.Function):
             ops.bn_bwd_reduce(dy, y, x, work, dz, partials, M, C, msplit,
                               ctx.relu, ctx.slope)
             ops.bn_bwd_grads(partials, msplit, bsums, dgamma, dbeta, C)
+            if ctx.frozen_stats:
+                # eval mode: the batch terms of dx vanish, dx = scale * dz.
+                # Zeroed sums make b0 = b1 = 0 in the apply kernel, which
+                # leaves exactly that one fp32 product (dgamma/dbeta above
+                # are the same in both modes).
+                bsums.zero_()
             ops.bn_bwd_apply(dz, x, work, bsums, dx, M, C)
         return (dx,
                 dgamma if need_g and not g_direct else None,
@@ -540,7 +548,13 @@ class MaxPool2d(nn.Module):
 
 
 class BatchNorm2d(nn.Module):
-    """NHWC training BatchNorm with optional fused residual-add + ReLU."""
+    """NHWC training BatchNorm with optional fused residual-add + ReLU.
+
+    Training mode and every backward need ``num_features % 64 == 0`` (the
+    reduction kernels walk 64-channel groups; other widths raise
+    ``ValueError``); the eval-mode forward needs ``% 8``.  In eval mode the
+    running statistics are constants, so the input gradient is ``scale * dz``.
+    """
 
     def __init__(self, num_features: int, eps: float = 1e-5, momentum: float = 0.1):
         super().__init__()

@@ -832,14 +832,25 @@ def bn_msplit(M: int, C: int) -> int:
     return msplit
 
 
+def _bn_width(name: str, C: int, mult: int) -> None:
+    """The reductions walk 64-channel groups (grid C/64) and the combine and
+    elementwise kernels 8-channel octets (grid C/8, 16-byte lanes): any other
+    width would leave channels unwritten, so it is refused before a launch."""
+    if C < mult or C % mult:
+        raise ValueError(f"{name}: C = {C} must be a positive multiple of "
+                         f"{mult}")
+
+
 def bn_stats(x: torch.Tensor, partials: torch.Tensor, M: int, C: int,
              msplit: int) -> None:
+    _bn_width("bn_stats", C, 64)
     require().bn_stats(x.data_ptr(), partials.data_ptr(), M, C, msplit, _stream())
 
 
 def bn_finalize(partials, msplit: int, gamma, beta, rmean, rvar, work,
                 M: int, C: int, eps: float, momentum: float,
                 update_running: bool) -> None:
+    _bn_width("bn_finalize", C, 8)
     require().bn_finalize(partials.data_ptr(), msplit, gamma.data_ptr(),
                           beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(),
                           work.data_ptr(), M, C, eps, momentum,
@@ -848,6 +859,7 @@ def bn_finalize(partials, msplit: int, gamma, beta, rmean, rvar, work,
 
 def bn_apply(x, res, y, work, M: int, C: int, relu: bool,
              slope: float = 0.0) -> None:
+    _bn_width("bn_apply", C, 8)
     require().bn_apply(x.data_ptr(), res.data_ptr() if res is not None else 0,
                        y.data_ptr(), work.data_ptr(), M, C, relu, slope,
                        _stream())
@@ -855,6 +867,7 @@ def bn_apply(x, res, y, work, M: int, C: int, relu: bool,
 
 def bn_bwd_reduce(dy, y, x, work, dz_out, partials, M: int, C: int,
                   msplit: int, relu: bool, slope: float = 0.0) -> None:
+    _bn_width("bn_bwd_reduce", C, 64)
     require().bn_bwd_reduce(dy.data_ptr(), y.data_ptr(), x.data_ptr(),
                             work.data_ptr(), dz_out.data_ptr(),
                             partials.data_ptr(), M, C, msplit, relu, slope,
@@ -862,11 +875,13 @@ def bn_bwd_reduce(dy, y, x, work, dz_out, partials, M: int, C: int,
 
 
 def bn_bwd_grads(partials, msplit: int, bsums, dgamma, dbeta, C: int) -> None:
+    _bn_width("bn_bwd_grads", C, 8)
     require().bn_bwd_grads(partials.data_ptr(), msplit, bsums.data_ptr(),
                            dgamma.data_ptr(), dbeta.data_ptr(), C, _stream())
 
 
 def bn_bwd_apply(dz, x, work, bsums, dx, M: int, C: int) -> None:
+    _bn_width("bn_bwd_apply", C, 8)
     require().bn_bwd_apply(dz.data_ptr(), x.data_ptr(), work.data_ptr(),
                            bsums.data_ptr(), dx.data_ptr(), M, C, _stream())
 
@@ -879,7 +894,9 @@ def bn_small_plan(M: int, C: int) -> tp.Tuple[str, str]:
     over ``[M, C]``: forward "small" (finalize + apply in one kernel) or
     "chain"; backward one of :data:`BN_BWD_SMALL_FORMS` (reduce + grads +
     apply in one kernel, 8 channels per block, its rows kept in registers) or
-    "chain" (the separate kernels)."""
+    "chain" (the separate kernels).  ``C % 64 != 0`` is always ("chain",
+    "chain"), whose reductions then raise: no kernel produces such
+    statistics."""
     fwd, bwd = require().bn_small_plan(M, C)
     names = {v: k for k, v in BN_BWD_SMALL_FORMS.items()}
     return ("small" if fwd else "chain"), names[bwd]

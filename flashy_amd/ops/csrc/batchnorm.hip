@@ -740,10 +740,14 @@ static inline int bn_bwd_small_rows(int64_t M) {
 // M = 1024 (with and without the dz write) and loses at 3136 and 4096;
 // forward, whose block order is tied to combine_partials8, wins at 512 and
 // already loses at 1024.
+// C % 64 != 0 is declined although the forms could run C % 8 == 0: the
+// partials they read come from k_bn_stats or a conv epilogue, both 64-channel
+// groups, so such a BatchNorm has no forward statistics to begin with and
+// the wrappers of the chain refuse it.
 extern "C" void bn_small_plan(int64_t M, int C, int* fwd_form, int* bwd_form) {
     *fwd_form = 0;
     *bwd_form = 0;
-    if (M < 1 || C < 8 || C % 8) return;
+    if (M < 1 || C < 64 || C % 64) return;
     if (M <= 512) *fwd_form = 1;
     if (M <= 1024) *bwd_form = 1;
 }

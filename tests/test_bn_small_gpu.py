@@ -363,13 +363,14 @@ def test_eval_mode_keeps_the_chain(monkeypatch):
     msplit = ops.bn_msplit(M, C)
     part = torch.empty(msplit * 2 * C, dtype=torch.float32, device="cuda")
     bsums = torch.empty(2 * C, dtype=torch.float32, device="cuda")
-    dz, dx = torch.empty_like(dy), torch.empty_like(x16)
+    dz = torch.empty_like(dy)
     dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(beta)
     ops.bn_bwd_reduce(dy, y_c, x16, work, dz, part, M, C, msplit, True, 0.0)
     ops.bn_bwd_grads(part, msplit, bsums, dgamma, dbeta, C)
-    ops.bn_bwd_apply(dz, x16, work, bsums, dx, M, C)
     assert torch.equal(y, y_c)
-    assert torch.equal(x.grad, dx)
+    # running statistics do not depend on x: dx = scale * dz, one fp32
+    # product and one rounding (not the training formula's batch terms)
+    assert torch.equal(x.grad, (scale * dz.float()).to(torch.bfloat16))
     assert torch.equal(rr.grad, dz)
     assert torch.equal(bn.weight.grad, dgamma)
     assert torch.equal(bn.bias.grad, dbeta)

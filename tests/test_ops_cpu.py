@@ -1,5 +1,6 @@
 # Copyright (c) Flashy-AMD authors.
 """CPU-checkable pieces of the ops layer: dim inference and launch plans."""
+import pytest
 import torch
 
 from flashy_amd import ops
@@ -60,6 +61,35 @@ def test_underfill_zn():
     assert ops._underfill_zn(3136, 512, 27) == 3
     assert ops._underfill_zn(3136, 512, 15) == 0     # short reduction
     assert ops._underfill_zn(64 * 56 * 56, 256, 64) == 0   # grid already full
+
+
+def test_bn_wrappers_refuse_widths_before_touching_the_extension(monkeypatch):
+    """The reductions walk 64-channel groups, the rest 8-channel octets; the
+    check runs before the extension is even loaded, so nothing is launched."""
+    def no_ext():
+        raise AssertionError("extension reached")
+
+    monkeypatch.setattr(ops, "require", no_ext)
+    t = torch.zeros(8)
+    for C in (0, 8, 32, 96):
+        with pytest.raises(ValueError):
+            ops.bn_stats(t, t, 4, C, 1)
+        with pytest.raises(ValueError):
+            ops.bn_bwd_reduce(t, t, t, t, t, t, 4, C, 1, False)
+    for C in (0, 4, 12, 60):
+        with pytest.raises(ValueError):
+            ops.bn_finalize(t, 1, t, t, t, t, t, 4, C, 1e-5, 0.1, False)
+        with pytest.raises(ValueError):
+            ops.bn_apply(t, None, t, t, 4, C, False)
+        with pytest.raises(ValueError):
+            ops.bn_bwd_grads(t, 1, t, t, t, C)
+        with pytest.raises(ValueError):
+            ops.bn_bwd_apply(t, t, t, t, t, 4, C)
+    # accepted widths get as far as the extension
+    for call in (lambda: ops.bn_stats(t, t, 4, 128, 1),
+                 lambda: ops.bn_apply(t, None, t, t, 4, 40, False)):
+        with pytest.raises(AssertionError, match="extension reached"):
+            call()
 
 
 def test_bn_msplit_alignment():
