@@ -17,13 +17,20 @@ from . import ops
 from .data import MixedTarget
 
 
+def _grad_buffer(x: torch.Tensor) -> torch.Tensor:
+    """The kernels write the gradient row-major: a contiguous buffer, never
+    ``empty_like``, which keeps the strides of a dense permuted input."""
+    return torch.empty(x.shape, dtype=x.dtype, device=x.device)
+
+
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         B, C = logits.shape
-        dlogits = torch.empty_like(logits)
+        dlogits = _grad_buffer(logits)
         loss = torch.zeros((), dtype=torch.float32, device=logits.device)
-        ops.cross_entropy_fwd_bwd(logits.contiguous(), target, dlogits, loss,
+        ops.cross_entropy_fwd_bwd(logits.contiguous(), target.contiguous(),
+                                  dlogits, loss,
                                   loss_scale=1.0 / B, grad_scale=1.0 / B)
         ctx.save_for_backward(dlogits)
         return loss
@@ -40,7 +47,7 @@ class _CrossEntropyMix(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, target_b, lam, eps: float):
         B, C = logits.shape
-        dlogits = torch.empty_like(logits)
+        dlogits = _grad_buffer(logits)
         loss = torch.zeros((), dtype=torch.float32, device=logits.device)
         ops.cross_entropy_mix_fwd_bwd(
             logits.contiguous(), target.contiguous(),
@@ -98,7 +105,7 @@ class _BCEWithLogits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, target_value: float) -> torch.Tensor:
         n = x.numel()
-        dx = torch.empty_like(x)
+        dx = _grad_buffer(x)
         loss = torch.zeros((), dtype=torch.float32, device=x.device)
         ops.bce_logits_fwd_bwd(x.contiguous(), dx, loss, target_value,
                                loss_scale=1.0 / n, grad_scale=1.0 / n)
@@ -123,7 +130,7 @@ class _MSE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         n = x.numel()
-        dx = torch.empty_like(x)
+        dx = _grad_buffer(x)
         loss = torch.zeros((), dtype=torch.float32, device=x.device)
         ops.mse_fwd_bwd(x.contiguous(), t.contiguous(), dx, loss,
                         loss_scale=1.0 / n, grad_scale=1.0 / n)
@@ -141,6 +148,10 @@ def mse_loss(x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
 
     Replaces F.mse_loss of the teacher-student workload
     (/root/reference/tests/dummy/train.py:93)."""
+    if x.shape != target.shape:
+        raise ValueError(f"mse_loss: target of shape {tuple(target.shape)} "
+                         f"against input of shape {tuple(x.shape)} (no "
+                         "broadcasting)")
     if x.device.type != "cuda":
         return torch.nn.functional.mse_loss(x, target)
     return _MSE.apply(x, target.detach())
@@ -153,5 +164,6 @@ def accuracy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         return (logits.argmax(1) == target).float().mean()
     B = logits.shape[0]
     out = torch.zeros((), dtype=torch.float32, device=logits.device)
-    ops.accuracy_count(logits.detach().contiguous(), target, out)
+    ops.accuracy_count(logits.detach().contiguous(), target.contiguous(),
+                       out)
     return out / B

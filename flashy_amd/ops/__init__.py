@@ -941,12 +941,36 @@ def bn_bwd_small(dy, y, x, work, dz, dgamma, dbeta, dx, M: int, C: int,
 # loss kernels (fused forward+input-grad; see flashy_amd/functional.py)
 # ---------------------------------------------------------------------------
 
+def _check_loss_out(x: torch.Tensor, dx: torch.Tensor,
+                    loss_sum: torch.Tensor) -> None:
+    """The kernels write ``dx`` row-major through its pointer and add into
+    ``loss_sum[0]``: ``dx`` is a contiguous twin of ``x``, ``loss_sum`` an
+    fp32 tensor on the same device."""
+    assert x.is_cuda and x.is_contiguous()
+    assert dx.is_contiguous() and dx.shape == x.shape
+    assert dx.dtype == x.dtype and dx.device == x.device
+    assert loss_sum.dtype == torch.float32 and loss_sum.numel() >= 1
+    assert loss_sum.device == x.device
+
+
+def _check_targets(logits: torch.Tensor, *targets) -> None:
+    B = logits.shape[0]
+    for t in targets:
+        if t is not None:
+            assert t.dtype == torch.int64 and tuple(t.shape) == (B,)
+            assert t.is_contiguous() and t.device == logits.device
+
+
 def cross_entropy_fwd_bwd(logits: torch.Tensor, target: torch.Tensor,
                           dlogits: torch.Tensor, loss_sum: torch.Tensor,
                           loss_scale: float, grad_scale: float) -> None:
+    """dlogits = (softmax - onehot) * grad_scale, loss_sum[0] += the rows'
+    loss * loss_scale.  A target outside [0, C) marks no class (its row's
+    loss is lse); nothing on the host checks the range."""
     ext = require()
     B, C = logits.shape
-    assert logits.is_contiguous() and target.dtype == torch.int64
+    _check_loss_out(logits, dlogits, loss_sum)
+    _check_targets(logits, target)
     ext.cross_entropy(logits.data_ptr(), target.data_ptr(), dlogits.data_ptr(),
                       loss_sum.data_ptr(), B, C, loss_scale, grad_scale,
                       _is_bf16(logits), _stream())
@@ -964,13 +988,8 @@ def cross_entropy_mix_fwd_bwd(logits: torch.Tensor, target: torch.Tensor,
     kernel reads (None: 1), so a captured launch follows its value."""
     ext = require()
     B, C = logits.shape
-    assert logits.is_contiguous() and logits.is_cuda
-    assert dlogits.is_contiguous() and dlogits.dtype == logits.dtype
-    assert tuple(dlogits.shape) == (B, C)
-    for t in (target, target_b):
-        if t is not None:
-            assert t.dtype == torch.int64 and tuple(t.shape) == (B,)
-            assert t.is_contiguous() and t.device == logits.device
+    _check_loss_out(logits, dlogits, loss_sum)
+    _check_targets(logits, target, target_b)
     if lam is not None:
         assert lam.dtype == torch.float32 and lam.numel() == 1
         assert lam.device == logits.device
@@ -987,7 +1006,7 @@ def bce_logits_fwd_bwd(x: torch.Tensor, dx: torch.Tensor,
                        loss_sum: torch.Tensor, target: float,
                        loss_scale: float, grad_scale: float) -> None:
     ext = require()
-    assert x.is_contiguous()
+    _check_loss_out(x, dx, loss_sum)
     ext.bce_logits(x.data_ptr(), dx.data_ptr(), loss_sum.data_ptr(), x.numel(),
                    target, loss_scale, grad_scale, _is_bf16(x), _stream())
 
@@ -996,7 +1015,9 @@ def mse_fwd_bwd(x: torch.Tensor, t: torch.Tensor, dx: torch.Tensor,
                 loss_sum: torch.Tensor, loss_scale: float,
                 grad_scale: float) -> None:
     ext = require()
-    assert x.is_contiguous() and t.is_contiguous() and x.dtype == t.dtype
+    _check_loss_out(x, dx, loss_sum)
+    assert t.is_contiguous() and t.dtype == x.dtype and t.shape == x.shape
+    assert t.device == x.device
     ext.mse(x.data_ptr(), t.data_ptr(), dx.data_ptr(), loss_sum.data_ptr(),
             x.numel(), loss_scale, grad_scale, _is_bf16(x), _stream())
 
@@ -1006,7 +1027,9 @@ def accuracy_count(logits: torch.Tensor, target: torch.Tensor,
     """out[0] += number of rows whose argmax == target (caller zeroes out)."""
     ext = require()
     B, C = logits.shape
-    assert logits.is_contiguous() and target.dtype == torch.int64
+    assert logits.is_cuda and logits.is_contiguous()
+    _check_targets(logits, target)
+    assert out.dtype == torch.float32 and out.device == logits.device
     ext.accuracy(logits.data_ptr(), target.data_ptr(), out.data_ptr(), B, C,
                  _is_bf16(logits), _stream())
 

@@ -17,6 +17,8 @@
 // One wave per row (C up to a few thousand; lanes stride the row).
 // Outputs: dlogits [B, C] = (softmax - onehot) * grad_scale, and
 // loss_sum[0] += sum_b (lse_b - logit_b[target_b]) * loss_scale.
+// A target outside [0, C) marks no class: its row's gradient is the softmax
+// alone and its loss is lse (as in k_cross_entropy_mix).
 // T: 0 = float32 logits, 1 = bfloat16 logits (fp32 math inside).
 // ---------------------------------------------------------------------------
 
@@ -73,7 +75,9 @@ k_cross_entropy(const T* __restrict__ logits, const int64_t* __restrict__ target
         store_f32(dx, c, grad);
     }
     if (lane == 0) {
-        float loss = (lse - load_f32(x, tgt)) * loss_scale;
+        // a target outside [0, C) matches no class above; do not read there
+        const float xt = tgt >= 0 && tgt < C ? load_f32(x, tgt) : 0.f;
+        float loss = (lse - xt) * loss_scale;
         atomicAdd(loss_sum, loss);
     }
 }
@@ -153,7 +157,10 @@ k_cross_entropy_mix(const T* __restrict__ logits,
         // a target outside [0, C) matches no class above; do not read there
         const float xa = ta >= 0 && ta < C ? load_f32(x, ta) : 0.f;
         const float xb = tb >= 0 && tb < C ? load_f32(x, tb) : 0.f;
-        float loss = lse - (wa * xa + wb * xb + uni * sx);
+        // without smoothing the mean has no weight: leave it out, so that a
+        // -inf logit outside the targets keeps the loss finite (0 * -inf)
+        const float mean = eps > 0.f ? uni * sx : 0.f;
+        float loss = lse - (wa * xa + wb * xb + mean);
         atomicAdd(loss_sum, loss * loss_scale);
     }
 }
