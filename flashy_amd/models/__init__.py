@@ -7,9 +7,10 @@ here, so the architectures the benchmark configs name are implemented
 in-house: ResNet-18/50 (CIFAR and ImageNet stems) and the DCGAN-style 64x64
 generator/discriminator pair used by the adversarial workload.
 """
-from .resnet import ResNet, resnet18, resnet50  # noqa: F401
+from .resnet import (ResNet, resnet18, resnet50,  # noqa: F401
+                     resnext50_32x4d)
 from .resnet_native import (NativeResNet, native_resnet18,  # noqa: F401
-                            native_resnet50)
+                            native_resnet50, native_resnext50_32x4d)
 from .dcgan import DCGANGenerator, DCGANDiscriminator  # noqa: F401
 from .dcgan_native import (NativeDCGANGenerator,  # noqa: F401
                            NativeDCGANDiscriminator)

@@ -13,8 +13,10 @@ import torch
 from torch import nn
 
 
-def _conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
-    return nn.Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False)
+def _conv3x3(cin: int, cout: int, stride: int = 1,
+             groups: int = 1) -> nn.Conv2d:
+    return nn.Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False,
+                     groups=groups)
 
 
 def _conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
@@ -45,13 +47,15 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, cin: int, planes: int, stride: int = 1,
-                 downsample: tp.Optional[nn.Module] = None):
+                 downsample: tp.Optional[nn.Module] = None,
+                 groups: int = 1, base_width: int = 64):
         super().__init__()
-        self.conv1 = _conv1x1(cin, planes)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = _conv3x3(planes, planes, stride)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = _conv1x1(planes, planes * self.expansion)
+        width = planes * base_width // 64 * groups   # ResNeXt width
+        self.conv1 = _conv1x1(cin, width)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = _conv3x3(width, width, stride, groups)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = _conv1x1(width, planes * self.expansion)
         self.bn3 = nn.BatchNorm2d(planes * self.expansion)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
@@ -66,9 +70,15 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, block: type, layers: tp.Sequence[int], num_classes: int = 1000,
-                 small_input: bool = False):
-        """``small_input=True`` uses the CIFAR stem (3x3 conv, no max-pool)."""
+                 small_input: bool = False, groups: int = 1,
+                 base_width: int = 64):
+        """``small_input=True`` uses the CIFAR stem (3x3 conv, no max-pool);
+        ``groups`` / ``base_width`` make a ResNeXt of a Bottleneck net."""
         super().__init__()
+        if (groups, base_width) != (1, 64) and block is not Bottleneck:
+            raise ValueError("groups / base_width need Bottleneck")
+        self.block_args = {} if block is not Bottleneck else \
+            {"groups": groups, "base_width": base_width}
         self.inplanes = 64
         if small_input:
             self.stem = nn.Sequential(
@@ -98,9 +108,11 @@ class ResNet(nn.Module):
             downsample = nn.Sequential(
                 _conv1x1(self.inplanes, planes * block.expansion, stride),
                 nn.BatchNorm2d(planes * block.expansion))
-        blocks = [block(self.inplanes, planes, stride, downsample)]
+        blocks = [block(self.inplanes, planes, stride, downsample,
+                        **self.block_args)]
         self.inplanes = planes * block.expansion
-        blocks += [block(self.inplanes, planes) for _ in range(1, n)]
+        blocks += [block(self.inplanes, planes, **self.block_args)
+                   for _ in range(1, n)]
         return nn.Sequential(*blocks)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -116,3 +128,8 @@ def resnet18(num_classes: int = 1000, small_input: bool = False) -> ResNet:
 
 def resnet50(num_classes: int = 1000, small_input: bool = False) -> ResNet:
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, small_input)
+
+
+def resnext50_32x4d(num_classes: int = 1000, small_input: bool = False) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, small_input,
+                  groups=32, base_width=4)

@@ -1,5 +1,5 @@
 # Copyright (c) Flashy-AMD authors.
-"""ResNet-18/50 on the native NHWC gfx950 kernel path.
+"""ResNet-18/50 and ResNeXt-50 32x4d on the native NHWC gfx950 kernel path.
 
 Same architecture as :mod:`flashy_amd.models.resnet` but built from
 ``flashy_amd.nn.Conv2d`` / ``BatchNorm2d``: bf16 NHWC activations, MFMA
@@ -49,13 +49,17 @@ class NativeBottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, cin: int, planes: int, stride: int = 1,
-                 downsample: bool = False):
+                 downsample: bool = False, groups: int = 1,
+                 base_width: int = 64):
         super().__init__()
-        self.conv1 = fnn.Conv2d(cin, planes, 1, feeds_bn=True)
-        self.bn1 = fnn.BatchNorm2d(planes)
-        self.conv2 = fnn.Conv2d(planes, planes, 3, stride, 1, feeds_bn=True)
-        self.bn2 = fnn.BatchNorm2d(planes)
-        self.conv3 = fnn.Conv2d(planes, planes * 4, 1, feeds_bn=True)
+        # ResNeXt: the 3x3 runs grouped at torchvision's width
+        width = planes * base_width // 64 * groups
+        self.conv1 = fnn.Conv2d(cin, width, 1, feeds_bn=True)
+        self.bn1 = fnn.BatchNorm2d(width)
+        self.conv2 = fnn.Conv2d(width, width, 3, stride, 1, feeds_bn=True,
+                                groups=groups)
+        self.bn2 = fnn.BatchNorm2d(width)
+        self.conv3 = fnn.Conv2d(width, planes * 4, 1, feeds_bn=True)
         self.bn3 = fnn.BatchNorm2d(planes * 4)
         if downsample:
             self.dconv = fnn.Conv2d(cin, planes * 4, 1, stride, 0, feeds_bn=True)
@@ -80,9 +84,14 @@ class NativeResNet(nn.Module):
     stem (224-class inputs, BASELINE config 5); default is the CIFAR stem."""
 
     def __init__(self, block: type, layers: tp.Sequence[int],
-                 num_classes: int = 10, imagenet_stem: bool = False):
+                 num_classes: int = 10, imagenet_stem: bool = False,
+                 groups: int = 1, base_width: int = 64):
         super().__init__()
         self.imagenet_stem = imagenet_stem
+        if (groups, base_width) != (1, 64) and block is not NativeBottleneck:
+            raise ValueError("groups / base_width need NativeBottleneck")
+        self.block_args = {} if block is not NativeBottleneck else \
+            {"groups": groups, "base_width": base_width}
         if imagenet_stem:
             self.stem_conv = fnn.Conv2d(3, 64, 7, 2, 3, input_grad=False)
             self.stem_pool = fnn.MaxPool2d(3, 2, 1)
@@ -100,9 +109,11 @@ class NativeResNet(nn.Module):
 
     def _make_layer(self, block: type, planes: int, n: int, stride: int = 1):
         downsample = stride != 1 or self.inplanes != planes * block.expansion
-        blocks = [block(self.inplanes, planes, stride, downsample)]
+        blocks = [block(self.inplanes, planes, stride, downsample,
+                        **self.block_args)]
         self.inplanes = planes * block.expansion
-        blocks += [block(self.inplanes, planes) for _ in range(1, n)]
+        blocks += [block(self.inplanes, planes, **self.block_args)
+                   for _ in range(1, n)]
         return nn.Sequential(*blocks)
 
     def enable_wt_cache(self) -> "NativeResNet":
@@ -172,3 +183,9 @@ def native_resnet50(num_classes: int = 10,
                     imagenet_stem: bool = False) -> NativeResNet:
     return NativeResNet(NativeBottleneck, [3, 4, 6, 3], num_classes,
                         imagenet_stem)
+
+
+def native_resnext50_32x4d(num_classes: int = 10,
+                           imagenet_stem: bool = False) -> NativeResNet:
+    return NativeResNet(NativeBottleneck, [3, 4, 6, 3], num_classes,
+                        imagenet_stem, groups=32, base_width=4)

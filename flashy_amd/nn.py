@@ -89,27 +89,91 @@ class _ConvFn(torch.autograd.Function):
                 None, None, None, None, None)
 
 
+def _gconv_dims(x_shape, K: int, stride: int, pad: int) -> ops.ConvDims:
+    N, H, W, C = x_shape
+    return ops.ConvDims(N, H, W, C, K, 3, 3, (H + 2 * pad - 3) // stride + 1,
+                        (W + 2 * pad - 3) // stride + 1, stride, pad)
+
+
+class _GroupedConvFn(torch.autograd.Function):
+    """Grouped 3x3 conv (csrc/conv_group.hip).  Emits no BatchNorm partials:
+    a following BatchNorm2d runs its own statistics pass."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, w: torch.Tensor, stride: int, pad: int,
+                groups: int, input_grad: bool):
+        w16 = _weight_bf16(w).contiguous()
+        x = x.contiguous()
+        d = _gconv_dims(x.shape, w.shape[0], stride, pad)
+        y = x.new_empty((d.N, d.Ho, d.Wo, d.K))
+        ops.gconv_fwd(x, w16, y, d, groups)
+        ctx.save_for_backward(x, w16)
+        ctx.dims = d
+        ctx.groups = groups
+        ctx.input_grad = input_grad
+        ctx.w_ref = w
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        x, w16 = ctx.saved_tensors
+        d: ops.ConvDims = ctx.dims
+        dy = dy.contiguous()
+        dw_buf = None
+        direct = True
+        if ctx.needs_input_grad[1]:  # skip wgrad entirely for frozen weights
+            dw_buf, direct = _grad_target(ctx.w_ref)
+            ops.gconv_wgrad(x, dy, dw_buf, d, ctx.groups)
+        dx = None
+        if ctx.input_grad:
+            dx = x.new_empty(x.shape)
+            ops.gconv_dgrad(dy, w16, dx, d, ctx.groups)
+        return (dx, dw_buf if dw_buf is not None and not direct else None,
+                None, None, None, None)
+
+
 class Conv2d(nn.Module):
-    """NHWC bf16 conv (no bias, as in ResNet).  Weight: [K, R, S, C] fp32."""
+    """NHWC bf16 conv (no bias, as in ResNet).  Weight: [K, R, S, C] fp32;
+    with ``groups > 1`` a grouped 3x3 conv with weight [K, 3, 3, C // groups]
+    (the shapes :func:`flashy_amd.ops.gconv_supported` accepts; anything
+    else raises ``ValueError`` here)."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int,
                  stride: int = 1, padding: int = 0, input_grad: bool = True,
-                 feeds_bn: bool = False):
+                 feeds_bn: bool = False, groups: int = 1):
         super().__init__()
         self.stride = stride
         self.padding = padding
         self.input_grad = input_grad
+        self.groups = groups
         # when the conv output goes straight into a training BatchNorm2d,
         # the conv epilogue emits the BN sum/sumsq partials for free
         self.feeds_bn = feeds_bn
         self._wt_view: tp.Optional[torch.Tensor] = None
         k = kernel_size
+        if groups != 1:
+            # the plan is dims-only and ignores the image size: probe 8x8
+            probe = ops.ConvDims(1, 8, 8, in_channels, out_channels, k, k,
+                                 (8 + 2 * padding - k) // stride + 1
+                                 if stride > 0 else 0,
+                                 (8 + 2 * padding - k) // stride + 1
+                                 if stride > 0 else 0, stride, padding)
+            if groups < 1 or in_channels % groups \
+                    or not ops.gconv_supported(probe, groups):
+                raise ValueError(
+                    f"{ops.GCONV_RULE}; got in={in_channels} "
+                    f"out={out_channels} kernel={k} stride={stride} "
+                    f"padding={padding} groups={groups}")
         self.weight = nn.Parameter(
-            torch.empty(out_channels, k, k, in_channels))
+            torch.empty(out_channels, k, k, in_channels // groups))
         fan_out = out_channels * k * k
         nn.init.normal_(self.weight, std=math.sqrt(2.0 / fan_out))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.groups != 1:
+            return _GroupedConvFn.apply(x, self.weight, self.stride,
+                                        self.padding, self.groups,
+                                        self.input_grad and x.requires_grad)
         return _ConvFn.apply(x, self.weight, self.stride, self.padding,
                              self.input_grad and x.requires_grad,
                              self._wt_view, self.feeds_bn and self.training)
@@ -128,6 +192,7 @@ class WtCache:
     def __init__(self, model: nn.Module):
         convs = [m for m in model.modules()
                  if isinstance(m, Conv2d) and m.input_grad
+                 and m.groups == 1   # grouped convs build their own operand
                  and m.weight.shape[-1] % 64 == 0]
         metas, total = [], 0
         mirrors = [getattr(c.weight, "_bf16_mirror", None) for c in convs]

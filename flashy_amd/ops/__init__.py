@@ -818,6 +818,91 @@ def conv_wgrad(x: torch.Tensor, dout: torch.Tensor, dw: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# grouped 3x3 convolution (csrc/conv_group.hip).  ``d`` carries the full
+# widths (d.C == d.K); grouped weights are [K, 3, 3, C // groups].
+# ---------------------------------------------------------------------------
+
+GCONV_RULE = ("grouped conv needs groups > 1, C == K, C % 64 == 0, "
+              "C // groups in {4, 8, 16, 32}, a 3x3 kernel, pad 1 and "
+              "stride 1 or 2")
+
+
+def gconv_supported(d: ConvDims, groups: int) -> bool:
+    """Whether the grouped kernels serve ``d`` with ``groups`` (dims only;
+    the plan lives in conv_group.hip)."""
+    return require().gconv_plan(*d, groups)[0] > 0
+
+
+def _gconv_check(d: ConvDims, groups: int, w: torch.Tensor, w_dtype,
+                 acts: tp.Sequence[tp.Tuple[torch.Tensor, tp.Tuple[int, ...]]]
+                 ) -> tp.Tuple[int, int]:
+    ci, splits = require().gconv_plan(*d, groups)
+    if not ci:
+        if d.stride in (1, 2) and (d.N < 1 or d.H < 1 or d.W < 1 or (d.Ho, d.Wo)
+                                   != ((d.H - 1) // d.stride + 1,
+                                       (d.W - 1) // d.stride + 1)):
+            raise ValueError(
+                "grouped conv needs N, H, W >= 1 and Ho, Wo = (H - 1) // "
+                f"stride + 1, (W - 1) // stride + 1; got {d}")
+        raise ValueError(f"{GCONV_RULE}; got {d} with groups={groups}")
+    assert w.dtype == w_dtype and w.is_cuda and w.is_contiguous()
+    assert tuple(w.shape) == (d.K, 3, 3, d.C // groups), (w.shape, d, groups)
+    for t, shape in acts:
+        assert t.dtype == torch.bfloat16 and t.is_cuda and t.is_contiguous()
+        assert tuple(t.shape) == shape, (t.shape, shape)
+        assert t.data_ptr() % 16 == 0, "16-byte lanes need an aligned tensor"
+    return ci, splits
+
+
+def _gconv_operand(w16: torch.Tensor, d: ConvDims, groups: int, ci: int,
+                   dgrad: bool) -> torch.Tensor:
+    """Chunk-major operand [K/16, 9, 16, Ci] of the grouped weights (the
+    backward-data one with ``dgrad``); one small launch, no host sync."""
+    wexp = torch.empty(d.K // 16, 9, 16, ci, dtype=torch.bfloat16,
+                       device=w16.device)
+    require().gconv_expand(w16.data_ptr(), wexp.data_ptr(), d.K,
+                           d.C // groups, dgrad, _stream())
+    return wexp
+
+
+def gconv_fwd(x: torch.Tensor, w16: torch.Tensor, y: torch.Tensor,
+              d: ConvDims, groups: int) -> None:
+    """y[N, Ho, Wo, K] = grouped conv of x[N, H, W, C] with the bf16 weights
+    ``w16`` [K, 3, 3, C // groups] (torch's grouping)."""
+    ci, _ = _gconv_check(d, groups, w16, torch.bfloat16,
+                         [(x, (d.N, d.H, d.W, d.C)),
+                          (y, (d.N, d.Ho, d.Wo, d.K))])
+    wexp = _gconv_operand(w16, d, groups, ci, False)
+    require().gconv_fwd(x.data_ptr(), wexp.data_ptr(), y.data_ptr(), *d,
+                        groups, _stream())
+
+
+def gconv_dgrad(dy: torch.Tensor, w16: torch.Tensor, dx: torch.Tensor,
+                d: ConvDims, groups: int) -> None:
+    """dx[N, H, W, C] from dy[N, Ho, Wo, K]; every element of dx is written."""
+    ci, _ = _gconv_check(d, groups, w16, torch.bfloat16,
+                         [(dy, (d.N, d.Ho, d.Wo, d.K)),
+                          (dx, (d.N, d.H, d.W, d.C))])
+    wexp = _gconv_operand(w16, d, groups, ci, True)
+    require().gconv_dgrad(dy.data_ptr(), wexp.data_ptr(), dx.data_ptr(), *d,
+                          groups, _stream())
+
+
+def gconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor,
+                d: ConvDims, groups: int) -> None:
+    """Accumulates (+=) the fp32 weight gradient [K, 3, 3, C // groups] into
+    ``dw``.  The m-splits write fp32 slices that a combine kernel sums in
+    split order: no atomics, bitwise repeatable."""
+    _, splits = _gconv_check(d, groups, dw, torch.float32,
+                             [(x, (d.N, d.H, d.W, d.C)),
+                              (dy, (d.N, d.Ho, d.Wo, d.K))])
+    assert dw.data_ptr() % 16 == 0
+    ws = torch.empty(splits, dw.numel(), dtype=torch.float32, device=x.device)
+    require().gconv_wgrad(x.data_ptr(), dy.data_ptr(), ws.data_ptr(),
+                          dw.data_ptr(), *d, groups, _stream())
+
+
+# ---------------------------------------------------------------------------
 # batchnorm kernels (NHWC training BN; see flashy_amd/nn.py)
 # ---------------------------------------------------------------------------
 

@@ -58,6 +58,15 @@ void launch_weight_transpose_batched(const void* src, void* dst,
                                      int64_t max_elems, hipStream_t stream);
 void launch_conv_wgrad(const void* x, const void* dout, void* dw, ConvDims d,
                        int n_splits, hipStream_t stream);
+int gconv_plan(ConvDims d, int groups, int* wgrad_splits);
+void launch_gconv_expand(const void* w16, void* wexp, int K, int Cg, int dgrad,
+                         hipStream_t stream);
+int launch_gconv_fwd(const void* x, const void* wexp, void* y, ConvDims d,
+                     int groups, hipStream_t stream);
+int launch_gconv_dgrad(const void* dy, const void* wexp, void* dx, ConvDims d,
+                       int groups, hipStream_t stream);
+int launch_gconv_wgrad(const void* x, const void* dy, void* ws, void* dw,
+                       ConvDims d, int groups, hipStream_t stream);
 void launch_bn_stats(const void* x, void* partials, int64_t M, int C,
                      int msplit, hipStream_t stream);
 void launch_bn_finalize(const void* partials, int msplit, const void* gamma,
@@ -370,6 +379,58 @@ PYBIND11_MODULE(_hip_ops, m) {
               launch_conv_wgrad((const void*)x, (const void*)dout, (void*)dw,
                                 make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
                                 n_splits, as_stream(stream));
+              check_last();
+          });
+    // grouped 3x3 conv (csrc/conv_group.hip): the plan's (Ci, wgrad splits),
+    // Ci = 0 where the grouped path does not serve the shape; the launchers
+    // take the expanded operand of gconv_expand
+    m.def("gconv_plan",
+          [](int N, int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad, int groups) {
+              int splits = 0;
+              const int ci = gconv_plan(
+                  make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad), groups,
+                  &splits);
+              return py::make_tuple(ci, splits);
+          });
+    m.def("gconv_expand",
+          [](uintptr_t w16, uintptr_t wexp, int K, int Cg, bool dgrad,
+             uintptr_t stream) {
+              launch_gconv_expand((const void*)w16, (void*)wexp, K, Cg,
+                                  dgrad ? 1 : 0, as_stream(stream));
+              check_last();
+          });
+    m.def("gconv_fwd",
+          [](uintptr_t x, uintptr_t wexp, uintptr_t y, int N, int H, int W,
+             int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
+             int groups, uintptr_t stream) {
+              if (!launch_gconv_fwd(
+                      (const void*)x, (const void*)wexp, (void*)y,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      groups, as_stream(stream)))
+                  throw std::invalid_argument("gconv_fwd: unsupported shape");
+              check_last();
+          });
+    m.def("gconv_dgrad",
+          [](uintptr_t dy, uintptr_t wexp, uintptr_t dx, int N, int H, int W,
+             int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
+             int groups, uintptr_t stream) {
+              if (!launch_gconv_dgrad(
+                      (const void*)dy, (const void*)wexp, (void*)dx,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      groups, as_stream(stream)))
+                  throw std::invalid_argument("gconv_dgrad: unsupported shape");
+              check_last();
+          });
+    m.def("gconv_wgrad",
+          [](uintptr_t x, uintptr_t dy, uintptr_t ws, uintptr_t dw, int N,
+             int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad, int groups, uintptr_t stream) {
+              if (!launch_gconv_wgrad(
+                      (const void*)x, (const void*)dy, (void*)ws, (void*)dw,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      groups, as_stream(stream)))
+                  throw std::invalid_argument("gconv_wgrad: unsupported shape");
               check_last();
           });
     m.def("bn_stats",
