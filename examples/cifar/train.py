@@ -9,8 +9,8 @@ import torch
 import flashy_amd
 from flashy_amd import distrib
 from flashy_amd.models import native_resnet18, resnet18
-from flashy_amd.optim import (LARS, FusedSGD, MultiStep, WarmupCosine,
-                              WarmupLinear, no_decay_1d)
+from flashy_amd.optim import (LARS, FusedLAMB, FusedSGD, MultiStep,
+                              WarmupCosine, WarmupLinear, no_decay_1d)
 from flashy_amd import xp as fxp
 
 from .solver import Solver, SyntheticCIFAR
@@ -52,6 +52,17 @@ def get_tensor_options(cfg):
         lars=lars)
 
 
+def get_lamb_options(cfg):
+    """The ``lamb:`` section -> the keywords FusedLAMB takes beyond
+    FusedSGD's, or None when it is off (the default): FusedSGD runs."""
+    section = cfg.get("lamb") or {}
+    if not section.get("enabled", False):
+        return None
+    return dict(trust_clip=bool(section.get("trust_clip", False)),
+                betas=tuple(section.get("betas", (0.9, 0.999))),
+                eps=section.get("eps", 1e-6))
+
+
 def get_solver(cfg):
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu") \
         if cfg.device == "auto" else torch.device(cfg.device)
@@ -62,19 +73,28 @@ def get_solver(cfg):
         loaders = _loaders(cfg)
         # schedule and clipping run on the device inside optim.step(), so
         # the captured step follows them under graph replay
-        optim = FusedSGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
-                         weight_decay=cfg.weight_decay, bf16_mirror=True,
-                         schedule=get_schedule(cfg, len(loaders["train"])),
-                         max_grad_norm=cfg.get("max_grad_norm"),
-                         **get_tensor_options(cfg))
+        common = dict(lr=cfg.lr, weight_decay=cfg.weight_decay,
+                      bf16_mirror=True,
+                      schedule=get_schedule(cfg, len(loaders["train"])),
+                      max_grad_norm=cfg.get("max_grad_norm"))
+        options, lamb = get_tensor_options(cfg), get_lamb_options(cfg)
+        if lamb is None:
+            optim = FusedSGD(model.parameters(), momentum=cfg.momentum,
+                             **common, **options)
+        elif options["lars"] is not None:
+            raise ValueError("lars.enabled and lamb.enabled exclude each other")
+        else:   # momentum is unused: betas take its place
+            optim = FusedLAMB(model.parameters(), **common, **lamb,
+                              param_options=options["param_options"])
         model.enable_wt_cache()
         return Solver(cfg, model, loaders, optim)
     if (cfg.get("schedule") or {}).get("kind") or cfg.get("max_grad_norm"):
         raise ValueError("schedule / max_grad_norm need the native path "
                          "(FusedSGD); this run uses torch.optim.SGD")
-    if any(v is not None for v in get_tensor_options(cfg).values()):
-        raise ValueError("no_decay_1d / lars need the native path (FusedSGD); "
-                         "this run uses torch.optim.SGD")
+    if any(v is not None for v in get_tensor_options(cfg).values()) or \
+            get_lamb_options(cfg) is not None:
+        raise ValueError("no_decay_1d / lars / lamb need the native path "
+                         "(FusedSGD, FusedLAMB); this run uses torch.optim.SGD")
     model = resnet18(num_classes=cfg.num_classes, small_input=True).to(device)
     distrib.broadcast_model(model)
     optim = torch.optim.SGD(model.parameters(), lr=cfg.lr,

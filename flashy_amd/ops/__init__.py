@@ -372,6 +372,80 @@ def fused_adam_seg(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
                        table.lr_scale.data_ptr(), _stream())
 
 
+# LAMB on the same chunk table: lamb_moments -> lamb_ratio -> lamb_apply, in
+# this order on one stream (csrc/fused_optim.hip, "LAMB")
+
+def _lamb_check(table: SegTable, partials: tp.Optional[torch.Tensor],
+                ratio: tp.Optional[torch.Tensor]) -> None:
+    for t, numel in ((partials, 2 * table.n_chunks),
+                     (ratio, table.n_tensors)):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_contiguous()
+            assert t.is_cuda and t.numel() == numel
+
+
+def lamb_moments(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
+                 v: torch.Tensor, beta1: float, beta2: float, eps: float,
+                 step: int, table: SegTable, partials: torch.Tensor,
+                 grad_scale: float = 1.0,
+                 step_dev: tp.Optional[torch.Tensor] = None,
+                 hyper: tp.Optional[torch.Tensor] = None) -> None:
+    """LAMB pass 1: move the Adam moments ``m`` / ``v`` in place with
+    ``g' = grad_scale * hyper[HYPER_COEF] * g`` and write per-chunk
+    ``(sum p^2, sum u^2)`` into the fp32 ``partials [C, 2]``, where
+    ``u = (m/bc1) / (sqrt(v/bc2) + eps) + wd * p`` is the update pass 2 will
+    apply (``wd`` per tensor from ``table``).  ``u`` is not stored and ``p`` /
+    ``g`` are not written.  No atomics, no pre-zeroing: every slot is written,
+    deterministic for a given table.  ``step`` / ``step_dev`` / ``hyper`` as
+    for :func:`fused_adam`.  Feed the partials to :func:`lamb_ratio`."""
+    ext = require()
+    assert p.dtype == torch.float32 and g.dtype == torch.float32
+    _seg_check(table, p, g, m, v)
+    _lamb_check(table, partials, None)
+    ext.lamb_moments(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                     step_dev.data_ptr() if step_dev is not None else 0,
+                     beta1, beta2, eps, step, grad_scale, _hyper_ptr(hyper),
+                     table.chunks.data_ptr(), table.n_chunks,
+                     table.wd.data_ptr(), partials.data_ptr(), _stream())
+
+
+def lamb_ratio(partials: torch.Tensor, table: SegTable, ratio: torch.Tensor,
+               trust_clip: bool = False) -> None:
+    """Write the LAMB trust ratio of every tensor of ``table`` into the fp32
+    ``ratio [T]``: ``|p| / |u|`` (at most 1 with ``trust_clip``) where the
+    tensor has ``lars_on`` set and both norms are positive, else exactly 1.
+    The chunk partials of :func:`lamb_moments` are summed per tensor in fixed
+    order in fp64; no host read."""
+    ext = require()
+    _lamb_check(table, partials, ratio)
+    ext.lamb_ratio(partials.data_ptr(), table.tensor_chunk.data_ptr(),
+                   table.lars_on.data_ptr(), ratio.data_ptr(),
+                   table.n_tensors, bool(trust_clip), _stream())
+
+
+def lamb_apply(p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float,
+               beta1: float, beta2: float, eps: float, step: int,
+               table: SegTable, ratio: torch.Tensor,
+               p_bf16: tp.Optional[torch.Tensor] = None,
+               step_dev: tp.Optional[torch.Tensor] = None,
+               hyper: tp.Optional[torch.Tensor] = None) -> None:
+    """LAMB pass 2: ``p -= lr * lr_scale * ratio * u`` per tensor, with ``u``
+    recomputed from the moments :func:`lamb_moments` left (same ``eps``,
+    ``step`` / ``step_dev`` and table) and ``ratio`` from :func:`lamb_ratio`;
+    writes ``p`` and the bf16 mirror.  The gradient is not read."""
+    ext = require()
+    assert p.dtype == torch.float32
+    _seg_check(table, p, m, v, p_bf16)
+    _lamb_check(table, None, ratio)
+    ext.lamb_apply(p.data_ptr(), m.data_ptr(), v.data_ptr(),
+                   p_bf16.data_ptr() if p_bf16 is not None else 0,
+                   step_dev.data_ptr() if step_dev is not None else 0,
+                   lr, beta1, beta2, eps, step, _hyper_ptr(hyper),
+                   table.chunks.data_ptr(), table.n_chunks,
+                   table.wd.data_ptr(), table.lr_scale.data_ptr(),
+                   ratio.data_ptr(), _stream())
+
+
 # ---------------------------------------------------------------------------
 # input ingest (uint8 NHWC -> bf16 NHWC; see flashy_amd/data.py)
 # ---------------------------------------------------------------------------

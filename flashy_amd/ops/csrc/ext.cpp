@@ -133,6 +133,20 @@ void launch_fused_adam_seg(void* p, const void* g, void* m, void* v,
                            float grad_scale, int adamw, const void* hyper,
                            const void* chunks, int n_chunks, const void* wd,
                            const void* lr_scale, hipStream_t stream);
+void launch_lamb_moments(void* p, const void* g, void* m, void* v,
+                         void* step_dev, float beta1, float beta2, float eps,
+                         int64_t step, float grad_scale, const void* hyper,
+                         const void* chunks, int n_chunks, const void* wd,
+                         void* partials, hipStream_t stream);
+void launch_lamb_ratio(const void* partials, const void* tensor_chunk,
+                       const void* trust_on, void* ratio, int n_tensors,
+                       int trust_clip, hipStream_t stream);
+void launch_lamb_apply(void* p, void* m, void* v, void* p_bf16,
+                       void* step_dev, float lr, float beta1, float beta2,
+                       float eps, int64_t step, const void* hyper,
+                       const void* chunks, int n_chunks, const void* wd,
+                       const void* lr_scale, const void* ratio,
+                       hipStream_t stream);
 void launch_image_ingest(const void* src, void* out, const void* step_dev,
                          int N, int H, int W, int OH, int OW, int pad,
                          uint64_t seed, uint32_t flip_thresh,
@@ -637,6 +651,46 @@ PYBIND11_MODULE(_hip_ops, m) {
                                     (const void*)chunks, n_chunks,
                                     (const void*)wd, (const void*)lr_scale,
                                     as_stream(stream));
+              check_last();
+          });
+    // LAMB: moments + per-chunk (sum p^2, sum u^2), per-tensor trust ratio,
+    // apply; three launches in this order on one stream
+    m.def("lamb_moments",
+          [](uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t var,
+             uintptr_t step_dev, float beta1, float beta2, float eps,
+             int64_t step, float grad_scale, uintptr_t hyper,
+             uintptr_t chunks, int n_chunks, uintptr_t wd, uintptr_t partials,
+             uintptr_t stream) {
+              launch_lamb_moments((void*)p, (const void*)g, (void*)mom,
+                                  (void*)var, (void*)step_dev, beta1, beta2,
+                                  eps, step, grad_scale, (const void*)hyper,
+                                  (const void*)chunks, n_chunks,
+                                  (const void*)wd, (void*)partials,
+                                  as_stream(stream));
+              check_last();
+          });
+    m.def("lamb_ratio",
+          [](uintptr_t partials, uintptr_t tensor_chunk, uintptr_t trust_on,
+             uintptr_t ratio, int n_tensors, bool trust_clip,
+             uintptr_t stream) {
+              launch_lamb_ratio((const void*)partials,
+                                (const void*)tensor_chunk,
+                                (const void*)trust_on, (void*)ratio, n_tensors,
+                                trust_clip ? 1 : 0, as_stream(stream));
+              check_last();
+          });
+    m.def("lamb_apply",
+          [](uintptr_t p, uintptr_t mom, uintptr_t var, uintptr_t p_bf16,
+             uintptr_t step_dev, float lr, float beta1, float beta2,
+             float eps, int64_t step, uintptr_t hyper, uintptr_t chunks,
+             int n_chunks, uintptr_t wd, uintptr_t lr_scale, uintptr_t ratio,
+             uintptr_t stream) {
+              launch_lamb_apply((void*)p, (void*)mom, (void*)var,
+                                (void*)p_bf16, (void*)step_dev, lr, beta1,
+                                beta2, eps, step, (const void*)hyper,
+                                (const void*)chunks, n_chunks, (const void*)wd,
+                                (const void*)lr_scale, (const void*)ratio,
+                                as_stream(stream));
               check_last();
           });
     // uint8 NHWC -> bf16 NHWC crop / flip / normalize (csrc/ingest.hip);

@@ -35,6 +35,13 @@ tells the kernels where each tensor lies in the flat buffer; the layout of
 the buffer itself never changes, and an optimizer built without them launches
 exactly the unsegmented kernels.  The trust ratios are computed on the device
 from the hyper block, so they too are correct under graph replay.
+
+:class:`FusedLAMB` puts the trust ratio on the Adam update instead of the
+gradient.  Its norm exists only after the moments have moved, so the step is
+two passes over the flat buffers with a per-tensor reduction between them
+(three launches, the update recomputed in the second pass, not stored); it
+is always segmented, and shares the chunk table, the per-tensor options, the
+hyper block and the device step counter with the other two.
 """
 from __future__ import annotations
 
@@ -208,7 +215,8 @@ _GROUP_KEYS = ("params", "weight_decay", "lr", "lars")
 
 def no_decay_1d(p: torch.nn.Parameter) -> tp.Dict[str, tp.Any]:
     """``param_options`` callable for the usual BatchNorm / bias exemption:
-    no weight decay and no LARS on tensors with ``ndim <= 1``."""
+    no weight decay and no layer-wise trust ratio (LARS / LAMB) on tensors
+    with ``ndim <= 1``."""
     if p.ndim <= 1:
         return {"weight_decay": 0.0, "lars": False}
     return {}
@@ -325,9 +333,14 @@ class FlatOptimizer:
     ``(param) -> options or None`` or a mapping ``param -> options`` with the
     keys ``weight_decay``, ``lr_scale`` and ``lars``, which keeps the
     parameters packed in the model's own order (e.g.
-    ``param_options=no_decay_1d``)."""
+    ``param_options=no_decay_1d``).  ``lars`` is the layer-wise trust ratio
+    (LARS on FusedSGD, LAMB on FusedLAMB)."""
 
     _SUPPORTS_LARS = False
+    # FusedLAMB: a trust ratio is part of the method, so it is on for every
+    # tensor whose ``lars`` option is not False and the step is always
+    # segmented
+    _LAMB = False
 
     def __init__(self, params: ParamsT, defaults: tp.Dict[str, tp.Any],
                  bf16_mirror: bool = False,
@@ -412,7 +425,8 @@ class FlatOptimizer:
         wd = self.defaults["weight_decay"]
         return [(wd if o["weight_decay"] is None else o["weight_decay"],
                  o["lr_scale"],
-                 self.lars is not None if o["lars"] is None else o["lars"])
+                 (self._LAMB or self.lars is not None) if o["lars"] is None
+                 else o["lars"])
                 for o in group.options]
 
     def _configure_segments(self) -> None:
@@ -422,12 +436,12 @@ class FlatOptimizer:
         captured step sees restored options."""
         resolved = [self._resolved(g) for g in self.groups]
         wd = self.defaults["weight_decay"]
-        uses_lars = any(r[2] for rs in resolved for r in rs)
-        if uses_lars and not self._SUPPORTS_LARS:
+        uses_lars = self._LAMB or any(r[2] for rs in resolved for r in rs)
+        if uses_lars and not (self._SUPPORTS_LARS or self._LAMB):
             raise NotImplementedError(
                 f"'lars': True on {type(self).__name__}: LARS is implemented "
                 f"for FusedSGD only")
-        if uses_lars and self.lars is None:
+        if uses_lars and self.lars is None and not self._LAMB:
             raise ValueError("'lars': True needs lars=LARS(...) on the "
                              "optimizer")
         self._segmented = uses_lars or any(
@@ -452,10 +466,10 @@ class FlatOptimizer:
 
     @property
     def last_trust_ratios(self) -> tp.Optional[tp.List[torch.Tensor]]:
-        """LARS trust ratios of the last step: one fp32 tensor per flat group
-        (see ``param_buffers``), on that group's device, one entry per
-        parameter in packing order (1 where LARS is off or a norm is 0).  No
-        sync.  ``None`` without LARS."""
+        """LARS (FusedSGD) or LAMB (FusedLAMB) trust ratios of the last step:
+        one fp32 tensor per flat group (see ``param_buffers``), on that
+        group's device, one entry per parameter in packing order (1 where the
+        ratio is off or a norm is 0).  No sync.  ``None`` without either."""
         if not any(g.ratio is not None for g in self.groups):
             return None
         return [g.ratio for g in self.groups]
@@ -860,3 +874,95 @@ class FusedAdam(FlatOptimizer):
             mine.copy_(got.to(mine.device))
         for mine, got in zip(self._exp_avg_sq, state.get("exp_avg_sq", [])):
             mine.copy_(got.to(mine.device))
+
+
+class FusedLAMB(FlatOptimizer):
+    """LAMB (timm's ``Lamb`` with ``always_adapt=False``): Adam moments and a
+    layer-wise trust ratio on the Adam update, as two fused HIP passes over
+    the flat buffers with a per-tensor reduction between them.  Per tensor
+    ``t``, with ``g' = clip_coef * g``::
+
+        m = b1*m + (1-b1)*g' ; v = b2*v + (1-b2)*g'^2
+        u = (m/bc1) / (sqrt(v/bc2) + eps) + wd_t * p
+        r_t = |p| / |u|  if the ratio is on for t and |p| > 0 and |u| > 0
+              1          otherwise        (min(r_t, 1) with trust_clip)
+        p -= lr * lr_scale_t * r_t * u
+
+    Weight decay sits inside ``u``, so the trust ratio scales it too.  The
+    ratio is on for every tensor; the per-tensor option (or param group key)
+    ``lars: False`` turns it off, so ``param_options=no_decay_1d`` is the
+    usual recipe.  The norms are taken on the device each step
+    (``last_trust_ratios``), and schedules, ``max_grad_norm``, param groups,
+    checkpoints and the bf16 mirror work as on :class:`FusedAdam`, whose
+    state-dict layout this shares."""
+
+    _LAMB = True
+
+    def __init__(self, params: ParamsT, lr: float,
+                 betas: tp.Tuple[float, float] = (0.9, 0.999),
+                 eps: float = 1e-6, weight_decay: float = 0.0,
+                 trust_clip: bool = False, bf16_mirror: bool = False,
+                 schedule: tp.Optional[LRSchedule] = None,
+                 max_grad_norm: tp.Optional[float] = None,
+                 param_options: tp.Optional[ParamOptionsT] = None):
+        super().__init__(params, dict(lr=lr, beta1=betas[0], beta2=betas[1],
+                                      eps=eps, weight_decay=weight_decay,
+                                      trust_clip=bool(trust_clip)),
+                         bf16_mirror, schedule, max_grad_norm, param_options)
+        self._exp_avg = [g.buffers_like() for g in self.groups]
+        self._exp_avg_sq = [g.buffers_like() for g in self.groups]
+        # bias correction (and a schedule) read the device step counter, so
+        # a captured step stays correct under replay
+        self._make_step_counters()
+
+    def _step_group(self, group: _Group) -> None:
+        d = self.defaults
+        i = self.groups.index(group)
+        m, v = self._exp_avg[i], self._exp_avg_sq[i]
+        if group.device.type == "cuda":
+            step_dev = self._step_dev[group.device]
+            hyper = self._hyper.get(group.device)
+            ops.lamb_moments(group.flat_p, group.flat_g, m, v, d["beta1"],
+                             d["beta2"], d["eps"], self.step_count, group.seg,
+                             group.seg_partials, step_dev=step_dev,
+                             hyper=hyper)
+            ops.lamb_ratio(group.seg_partials, group.seg, group.ratio,
+                           d["trust_clip"])
+            ops.lamb_apply(group.flat_p, m, v, d["lr"], d["beta1"],
+                           d["beta2"], d["eps"], self.step_count, group.seg,
+                           group.ratio, p_bf16=group.flat_p16,
+                           step_dev=step_dev, hyper=hyper)
+            return
+        # CPU fallback: the same math, tensor by tensor
+        lr, coef = self._lr_coef()
+        bc1 = 1 - d["beta1"] ** self.step_count
+        bc2 = 1 - d["beta2"] ** self.step_count
+        with torch.no_grad():
+            offset = 0
+            for t, (param, (wd, lr_scale, trust)) in enumerate(
+                    zip(group.params, self._resolved(group))):
+                sl = slice(offset, offset + param.numel())
+                offset = sl.stop
+                p, g, mt, vt = group.flat_p[sl], group.flat_g[sl], m[sl], v[sl]
+                if coef is not None:
+                    g = g * coef
+                mt.mul_(d["beta1"]).add_(g, alpha=1 - d["beta1"])
+                vt.mul_(d["beta2"]).addcmul_(g, g, value=1 - d["beta2"])
+                u = (mt / bc1).div_((vt / bc2).sqrt_().add_(d["eps"]))
+                if wd != 0:
+                    u.add_(p, alpha=wd)
+                ratio = 1.0
+                if trust:
+                    wn = float(p.double().norm())
+                    un = float(u.double().norm())
+                    if wn > 0 and un > 0:
+                        ratio = wn / un
+                        if d["trust_clip"]:
+                            ratio = min(ratio, 1.0)
+                group.ratio[t] = ratio
+                p.add_(u, alpha=-lr * lr_scale * ratio)
+            group.refresh_bf16()
+
+    # the moments are saved and restored as FusedAdam's
+    _extra_state = FusedAdam._extra_state
+    _load_extra_state = FusedAdam._load_extra_state

@@ -20,7 +20,17 @@ ResNet-50's own tensors (shapes from ``flashy_amd.models.resnet50``):
   no_decay_1d  k_fused_sgd_seg through the chunk table, BN / bias exempt
   lars         + k_seg_sqsum + k_lars_prepare: the full LARS step
 
-Run on the GPU: PYTHONPATH=. python scripts/optim_step_cost.py [--groups]
+With ``--lamb`` it times LAMB against Adam on the same arena, both with
+``no_decay_1d`` and a bf16 mirror:
+
+  adam_seg     k_fused_adam_seg: 7.5 words per element
+  lamb         k_lamb_moments_seg + k_lamb_ratio + k_lamb_apply_seg: 10.5
+
+and the two LAMB passes alone.  The five fp32 / bf16 buffers of the step are
+460 MB, larger than the 256 MB last-level cache.
+
+Run on the GPU: PYTHONPATH=. python scripts/optim_step_cost.py
+                [--groups | --lamb]
 """
 import argparse
 import statistics
@@ -28,7 +38,8 @@ import statistics
 import torch
 
 import flashy_amd.ops as ops
-from flashy_amd.optim import LARS, FusedSGD, WarmupCosine, no_decay_1d
+from flashy_amd.optim import (LARS, FusedAdam, FusedLAMB, FusedSGD,
+                              WarmupCosine, no_decay_1d)
 
 R50_PARAMS = 25_557_032
 
@@ -109,6 +120,58 @@ def groups_main(args):
           f"{8 * n / t_norm / 1e6:.2f} TB/s")
 
 
+def lamb_main(args):
+    shapes = r50_shapes()
+    n = sum(torch.Size(s).numel() for s in shapes)
+
+    def make(klass, **kw):
+        params = [torch.nn.Parameter(torch.randn(s, device="cuda") * 0.02)
+                  for s in shapes]
+        opt = klass(params, lr=1e-3, weight_decay=1e-2, bf16_mirror=True,
+                    param_options=no_decay_1d, **kw)
+        opt.grad_buffers[0].normal_(std=1e-3)
+        return opt
+
+    adam, lamb = make(FusedAdam, adamw=True), make(FusedLAMB)
+    assert adam.groups[0].seg is not None
+    # the passes alone run on a buffer set of their own, so the timed
+    # optimizers stay independent of them
+    alone = make(FusedLAMB)
+    group, table = alone.groups[0], alone.groups[0].seg
+    m, v = alone._exp_avg[0], alone._exp_avg_sq[0]
+    step_dev = alone._step_dev[group.device]
+    # pass 2 alone would repeat one ratio on moving weights, which need not
+    # be stable; a ratio of 0 moves the same bytes and leaves p where it is
+    no_step = torch.zeros_like(group.ratio)
+    timed = {
+        "adam_seg": adam.step,
+        "lamb": lamb.step,
+        "k_lamb_moments_seg alone": lambda: ops.lamb_moments(
+            group.flat_p, group.flat_g, m, v, 0.9, 0.999, 1e-6, 0, table,
+            group.seg_partials, step_dev=step_dev),
+        "k_lamb_apply_seg alone": lambda: ops.lamb_apply(
+            group.flat_p, m, v, 1e-3, 0.9, 0.999, 1e-6, 0, table, no_step,
+            p_bf16=group.flat_p16, step_dev=step_dev),
+    }
+    results = time_alternating(timed, args.rounds, args.iters)
+    assert torch.isfinite(lamb.groups[0].flat_p).all()
+
+    print(f"arena: {n} floats in {len(shapes)} tensors, {table.n_chunks} "
+          f"chunks of <= {ops.SEG_CHUNK}; {args.rounds} rounds x "
+          f"{args.iters} steps")
+    print(f"{'config':<26} {'median us':>10} {'min':>8} {'max':>8} "
+          f"{'vs adam':>8} {'TB/s':>6}")
+    # bytes the algorithm needs per element: Adam p g m v in, p m v bf16 out;
+    # LAMB pass 1 p g m v in, m v out; pass 2 p m v in, p bf16 out
+    words = {"adam_seg": 7.5, "lamb": 10.5, "k_lamb_moments_seg alone": 6.0,
+             "k_lamb_apply_seg alone": 4.5}
+    t_adam = statistics.median(results["adam_seg"])
+    for name, ts in results.items():
+        med = statistics.median(ts)
+        print(f"{name:<26} {med:>10.1f} {min(ts):>8.1f} {max(ts):>8.1f} "
+              f"{med / t_adam:>8.3f} {4 * words[name] * n / med / 1e6:>6.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=R50_PARAMS)
@@ -116,12 +179,17 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--groups", action="store_true",
                     help="time the per-tensor / LARS path instead")
+    ap.add_argument("--lamb", action="store_true",
+                    help="time FusedLAMB against segmented FusedAdam instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU: a CPU timing says nothing here")
     torch.manual_seed(0)
     if args.groups:
         groups_main(args)
+        return
+    if args.lamb:
+        lamb_main(args)
         return
     n = args.n
 
