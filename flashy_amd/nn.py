@@ -132,11 +132,52 @@ class _GroupedConvFn(torch.autograd.Function):
                 None, None, None, None)
 
 
+class _DepthwiseConvFn(torch.autograd.Function):
+    """Depthwise k x k conv (csrc/conv_depthwise.hip), weight [C, k, k, 1].
+    Emits no BatchNorm partials, as the grouped path."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, w: torch.Tensor, stride: int, pad: int,
+                input_grad: bool):
+        w16 = _weight_bf16(w).contiguous()
+        x = x.contiguous()
+        N, H, W, C = x.shape
+        k = w.shape[1]
+        d = ops.ConvDims(N, H, W, C, C, k, k, (H + 2 * pad - k) // stride + 1,
+                         (W + 2 * pad - k) // stride + 1, stride, pad)
+        y = x.new_empty((d.N, d.Ho, d.Wo, d.K))
+        ops.dwconv_fwd(x, w16, y, d)
+        ctx.save_for_backward(x, w16)
+        ctx.dims = d
+        ctx.input_grad = input_grad
+        ctx.w_ref = w
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        x, w16 = ctx.saved_tensors
+        d: ops.ConvDims = ctx.dims
+        dy = dy.contiguous()
+        dw_buf = None
+        direct = True
+        if ctx.needs_input_grad[1]:  # skip wgrad entirely for frozen weights
+            dw_buf, direct = _grad_target(ctx.w_ref)
+            ops.dwconv_wgrad(x, dy, dw_buf, d)
+        dx = None
+        if ctx.input_grad:
+            dx = x.new_empty(x.shape)
+            ops.dwconv_dgrad(dy, w16, dx, d)
+        return (dx, dw_buf if dw_buf is not None and not direct else None,
+                None, None, None)
+
+
 class Conv2d(nn.Module):
     """NHWC bf16 conv (no bias, as in ResNet).  Weight: [K, R, S, C] fp32;
     with ``groups > 1`` a grouped 3x3 conv with weight [K, 3, 3, C // groups]
-    (the shapes :func:`flashy_amd.ops.gconv_supported` accepts; anything
-    else raises ``ValueError`` here)."""
+    (the shapes :func:`flashy_amd.ops.gconv_supported` accepts), or, with
+    ``groups == in_channels == out_channels``, a depthwise k x k conv with
+    weight [C, k, k, 1] (:func:`flashy_amd.ops.dwconv_supported`); anything
+    else raises ``ValueError`` here."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int,
                  stride: int = 1, padding: int = 0, input_grad: bool = True,
@@ -151,6 +192,7 @@ class Conv2d(nn.Module):
         self.feeds_bn = feeds_bn
         self._wt_view: tp.Optional[torch.Tensor] = None
         k = kernel_size
+        self.depthwise = groups != 1 and groups == in_channels == out_channels
         if groups != 1:
             # the plan is dims-only and ignores the image size: probe 8x8
             probe = ops.ConvDims(1, 8, 8, in_channels, out_channels, k, k,
@@ -158,7 +200,13 @@ class Conv2d(nn.Module):
                                  if stride > 0 else 0,
                                  (8 + 2 * padding - k) // stride + 1
                                  if stride > 0 else 0, stride, padding)
-            if groups < 1 or in_channels % groups \
+            if self.depthwise:
+                if not ops.dwconv_supported(probe):
+                    raise ValueError(
+                        f"{ops.DWCONV_RULE}; got in={in_channels} "
+                        f"out={out_channels} kernel={k} stride={stride} "
+                        f"padding={padding} groups={groups}")
+            elif groups < 1 or in_channels % groups \
                     or not ops.gconv_supported(probe, groups):
                 raise ValueError(
                     f"{ops.GCONV_RULE}; got in={in_channels} "
@@ -170,6 +218,10 @@ class Conv2d(nn.Module):
         nn.init.normal_(self.weight, std=math.sqrt(2.0 / fan_out))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.depthwise:
+            return _DepthwiseConvFn.apply(x, self.weight, self.stride,
+                                          self.padding,
+                                          self.input_grad and x.requires_grad)
         if self.groups != 1:
             return _GroupedConvFn.apply(x, self.weight, self.stride,
                                         self.padding, self.groups,

@@ -977,6 +977,72 @@ def gconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# depthwise k x k convolution (csrc/conv_depthwise.hip).  ``d.C == d.K`` is
+# the channel count (groups == C is implied); weights are [C, k, k, 1] and
+# are read as they are: no prepared operand, no extra launch.
+# ---------------------------------------------------------------------------
+
+DWCONV_RULE = ("depthwise conv needs groups == in_channels == out_channels, "
+               "C % 8 == 0, a square kernel of 3, 5 or 7, padding "
+               "kernel // 2 and stride 1 or 2")
+
+
+def dwconv_supported(d: ConvDims) -> bool:
+    """Whether the depthwise kernels serve ``d`` (dims only; the plan lives
+    in conv_depthwise.hip)."""
+    return require().dwconv_plan(*d)[0] > 0
+
+
+def _dwconv_check(d: ConvDims, w: torch.Tensor, w_dtype,
+                  acts: tp.Sequence[tp.Tuple[torch.Tensor, tp.Tuple[int, ...]]]
+                  ) -> int:
+    ok, splits = require().dwconv_plan(*d)
+    if not ok:
+        raise ValueError(
+            f"{DWCONV_RULE}, N, H, W >= 1 and Ho, Wo = (H - 1) // stride + 1, "
+            f"(W - 1) // stride + 1; got {d}")
+    assert w.dtype == w_dtype and w.is_cuda and w.is_contiguous()
+    assert tuple(w.shape) == (d.C, d.R, d.S, 1), (w.shape, d)
+    for t, shape in acts:
+        assert t.dtype == torch.bfloat16 and t.is_cuda and t.is_contiguous()
+        assert tuple(t.shape) == shape, (t.shape, shape)
+        assert t.data_ptr() % 16 == 0, "16-byte lanes need an aligned tensor"
+    return splits
+
+
+def dwconv_fwd(x: torch.Tensor, w16: torch.Tensor, y: torch.Tensor,
+               d: ConvDims) -> None:
+    """y[N, Ho, Wo, C] = depthwise conv of x[N, H, W, C] with the bf16
+    weights ``w16`` [C, k, k, 1]."""
+    _dwconv_check(d, w16, torch.bfloat16, [(x, (d.N, d.H, d.W, d.C)),
+                                           (y, (d.N, d.Ho, d.Wo, d.C))])
+    require().dwconv_fwd(x.data_ptr(), w16.data_ptr(), y.data_ptr(), *d,
+                         _stream())
+
+
+def dwconv_dgrad(dy: torch.Tensor, w16: torch.Tensor, dx: torch.Tensor,
+                 d: ConvDims) -> None:
+    """dx[N, H, W, C] from dy[N, Ho, Wo, C]; every element of dx is written."""
+    _dwconv_check(d, w16, torch.bfloat16, [(dy, (d.N, d.Ho, d.Wo, d.C)),
+                                           (dx, (d.N, d.H, d.W, d.C))])
+    require().dwconv_dgrad(dy.data_ptr(), w16.data_ptr(), dx.data_ptr(), *d,
+                           _stream())
+
+
+def dwconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor,
+                 d: ConvDims) -> None:
+    """Accumulates (+=) the fp32 weight gradient [C, k, k, 1] into ``dw``.
+    The m-splits write fp32 slices that a combine kernel sums in split
+    order: no atomics, bitwise repeatable."""
+    splits = _dwconv_check(d, dw, torch.float32,
+                           [(x, (d.N, d.H, d.W, d.C)),
+                            (dy, (d.N, d.Ho, d.Wo, d.C))])
+    ws = torch.empty(splits, dw.numel(), dtype=torch.float32, device=x.device)
+    require().dwconv_wgrad(x.data_ptr(), dy.data_ptr(), ws.data_ptr(),
+                           dw.data_ptr(), *d, _stream())
+
+
+# ---------------------------------------------------------------------------
 # batchnorm kernels (NHWC training BN; see flashy_amd/nn.py)
 # ---------------------------------------------------------------------------
 

@@ -67,6 +67,13 @@ int launch_gconv_dgrad(const void* dy, const void* wexp, void* dx, ConvDims d,
                        int groups, hipStream_t stream);
 int launch_gconv_wgrad(const void* x, const void* dy, void* ws, void* dw,
                        ConvDims d, int groups, hipStream_t stream);
+int dwconv_plan(ConvDims d, int* wgrad_splits);
+int launch_dwconv_fwd(const void* x, const void* w16, void* y, ConvDims d,
+                      hipStream_t stream);
+int launch_dwconv_dgrad(const void* dy, const void* w16, void* dx, ConvDims d,
+                        hipStream_t stream);
+int launch_dwconv_wgrad(const void* x, const void* dy, void* ws, void* dw,
+                        ConvDims d, hipStream_t stream);
 void launch_bn_stats(const void* x, void* partials, int64_t M, int C,
                      int msplit, hipStream_t stream);
 void launch_bn_finalize(const void* partials, int msplit, const void* gamma,
@@ -445,6 +452,50 @@ PYBIND11_MODULE(_hip_ops, m) {
                       make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
                       groups, as_stream(stream)))
                   throw std::invalid_argument("gconv_wgrad: unsupported shape");
+              check_last();
+          });
+    // depthwise k x k conv (csrc/conv_depthwise.hip): the plan's (served,
+    // wgrad splits); the launchers read the bf16 weights [C][k][k][1] as
+    // they are, there is no prepared operand
+    m.def("dwconv_plan",
+          [](int N, int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad) {
+              int splits = 0;
+              const int ok = dwconv_plan(
+                  make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad), &splits);
+              return py::make_tuple(ok, splits);
+          });
+    m.def("dwconv_fwd",
+          [](uintptr_t x, uintptr_t w16, uintptr_t y, int N, int H, int W,
+             int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
+             uintptr_t stream) {
+              if (!launch_dwconv_fwd(
+                      (const void*)x, (const void*)w16, (void*)y,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      as_stream(stream)))
+                  throw std::invalid_argument("dwconv_fwd: unsupported shape");
+              check_last();
+          });
+    m.def("dwconv_dgrad",
+          [](uintptr_t dy, uintptr_t w16, uintptr_t dx, int N, int H, int W,
+             int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
+             uintptr_t stream) {
+              if (!launch_dwconv_dgrad(
+                      (const void*)dy, (const void*)w16, (void*)dx,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      as_stream(stream)))
+                  throw std::invalid_argument("dwconv_dgrad: unsupported shape");
+              check_last();
+          });
+    m.def("dwconv_wgrad",
+          [](uintptr_t x, uintptr_t dy, uintptr_t ws, uintptr_t dw, int N,
+             int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad, uintptr_t stream) {
+              if (!launch_dwconv_wgrad(
+                      (const void*)x, (const void*)dy, (void*)ws, (void*)dw,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      as_stream(stream)))
+                  throw std::invalid_argument("dwconv_wgrad: unsupported shape");
               check_last();
           });
     m.def("bn_stats",
