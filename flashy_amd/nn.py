@@ -688,3 +688,125 @@ class BatchNorm2d(nn.Module):
                 relu: bool = False, slope: float = 0.0) -> torch.Tensor:
         """``relu=True, slope=s`` applies LeakyReLU(s) (s=0: plain ReLU)."""
         return _BnFn.apply(x, self.weight, self.bias, res, relu, slope, self)
+
+
+def _param_grads(ctx, params: tp.Sequence[tp.Optional[torch.Tensor]],
+                 first: int):
+    """(kernel targets, autograd returns) for the fp32 parameters at inputs
+    ``first``, ...: a frozen or absent one gets no target and no gradient, a
+    live one accumulates straight into ``p.grad`` where that exists."""
+    targets, returns = [], []
+    for i, p in enumerate(params):
+        if p is None or not ctx.needs_input_grad[first + i]:
+            targets.append(None)
+            returns.append(None)
+            continue
+        buf, direct = _grad_target(p)
+        targets.append(buf)
+        returns.append(None if direct else buf)
+    return targets, returns
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """LayerNorm over the channels of an NHWC tensor (csrc/layernorm.hip);
+    saves the input and each row's (mean, rstd), not the output."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                in_bias: tp.Optional[torch.Tensor], eps: float):
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        stats = torch.empty(x.numel() // x.shape[-1], 2, dtype=torch.float32,
+                            device=x.device)
+        ops.ln_fwd(x, gamma, beta, y, stats, eps, in_bias)
+        ctx.save_for_backward(x, stats)
+        ctx.refs = (gamma, beta, in_bias)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        x, stats = ctx.saved_tensors
+        gamma, beta, in_bias = ctx.refs
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        (dgamma, dbeta, db_in), grads = _param_grads(
+            ctx, (gamma, beta, in_bias), 1)
+        ops.ln_bwd(dy.contiguous(), x, stats, gamma, dx, dgamma, dbeta,
+                   in_bias, db_in)
+        return (dx, *grads, None)
+
+
+class LayerNorm2d(nn.Module):
+    """LayerNorm over the channels of an NHWC bf16 tensor, NHWC out, fp32
+    ``weight`` / ``bias``; ``num_channels % 8 == 0``, at most 1024
+    (:data:`flashy_amd.ops.LN_RULE`).  ``forward(x, in_bias)`` normalizes
+    ``x + in_bias``: the bias of the conv that produced ``x`` folded in, so
+    it costs no pass of its own."""
+
+    def __init__(self, num_channels: int, eps: float = 1e-6):
+        super().__init__()
+        if num_channels < 8 or num_channels % 8 or num_channels > 1024:
+            raise ValueError(f"{ops.LN_RULE}; got {num_channels} channels")
+        self.num_channels = num_channels
+        self.eps = eps
+        self.weight = nn.Parameter(torch.ones(num_channels))
+        self.bias = nn.Parameter(torch.zeros(num_channels))
+
+    def forward(self, x: torch.Tensor,
+                in_bias: tp.Optional[torch.Tensor] = None) -> torch.Tensor:
+        return _LayerNormFn.apply(x, self.weight, self.bias, in_bias, self.eps)
+
+
+class _BiasGeluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h: torch.Tensor, bias: torch.Tensor):
+        h = h.contiguous()
+        g = torch.empty_like(h)
+        ops.bias_gelu_fwd(h, bias, g)
+        ctx.save_for_backward(h)
+        ctx.refs = (bias,)
+        return g
+
+    @staticmethod
+    def backward(ctx, dg: torch.Tensor):
+        (h,) = ctx.saved_tensors
+        (bias,) = ctx.refs
+        dh = torch.empty_like(h)
+        (db,), grads = _param_grads(ctx, (bias,), 1)
+        ops.bias_gelu_bwd(dg.contiguous(), h, bias, dh, db)
+        return (dh, *grads)
+
+
+def bias_gelu(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """``gelu(x + bias)`` (erf form) over NHWC bf16 ``x`` with an fp32
+    per-channel ``bias``, one launch; backward recomputes from ``x``."""
+    return _BiasGeluFn.apply(x, bias)
+
+
+class _ScaleResidualFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z: torch.Tensor, bias: torch.Tensor, scale: torch.Tensor,
+                res: torch.Tensor):
+        z = z.contiguous()
+        out = torch.empty_like(z)
+        ops.scale_residual_fwd(z, bias, scale, res.contiguous(), out)
+        ctx.save_for_backward(z)
+        ctx.refs = (bias, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        (z,) = ctx.saved_tensors
+        bias, scale = ctx.refs
+        dout = dout.contiguous()
+        dz = torch.empty_like(z)
+        (db, ds), grads = _param_grads(ctx, (bias, scale), 1)
+        ops.scale_residual_bwd(dout, z, bias, scale, dz, ds, db)
+        # the residual branch's gradient is dout itself, not a copy
+        return (dz, *grads, dout if ctx.needs_input_grad[3] else None)
+
+
+def scale_residual(z: torch.Tensor, bias: torch.Tensor, scale: torch.Tensor,
+                   res: torch.Tensor) -> torch.Tensor:
+    """``res + scale * (z + bias)`` over NHWC bf16 ``z`` / ``res`` with fp32
+    per-channel ``bias`` and layer ``scale``, one launch."""
+    return _ScaleResidualFn.apply(z, bias, scale, res)

@@ -1043,6 +1043,143 @@ def dwconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# channel LayerNorm, bias+GELU, layer scale + residual (csrc/layernorm.hip).
+# Activations are contiguous bf16 [..., C] (NHWC: M = the product of the
+# leading dims); parameters and their gradients are fp32 [C].  Gradient
+# targets are ACCUMULATED into, as the conv wgrads; a None target is skipped.
+# ---------------------------------------------------------------------------
+
+LN_RULE = ("channel LayerNorm needs C % 8 == 0 and 8 <= C <= 1024; bias+GELU "
+           "and scale+residual need C % 8 == 0 and C >= 8; at least one row")
+
+
+class LnPlan(tp.NamedTuple):
+    served: int          # 0 nothing, 1 elementwise families only, 2 LayerNorm too
+    lanes: int           # lanes per row
+    rows_per_block: int
+    grid: int
+    col_chunks: int      # grid.y of the elementwise kernels
+    slices: int          # fp32 column-sum slices a backward writes
+
+
+def ln_plan(M: int, C: int) -> LnPlan:
+    """What csrc/layernorm.hip decides for ``[M, C]`` (dims only)."""
+    return LnPlan(*require().ln_plan(M, C))
+
+
+def ln_supported(M: int, C: int) -> bool:
+    """Whether :func:`ln_fwd` / :func:`ln_bwd` serve ``[M, C]``."""
+    return ln_plan(M, C).served == 2
+
+
+def _ln_check(name: str, layernorm: bool, acts: tp.Sequence[torch.Tensor],
+              params: tp.Sequence[tp.Optional[torch.Tensor]]
+              ) -> tp.Tuple[int, int]:
+    """Everything that can be refused is refused here, before the extension
+    is loaded.  Returns (M, C)."""
+    x = acts[0]
+    C = x.shape[-1] if x.dim() else 0
+    M = x.numel() // C if C else 0
+    if M < 1 or C < 8 or C % 8 or (layernorm and C > 1024) or M >= 2 ** 31:
+        raise ValueError(f"{name}: {LN_RULE}; got M = {M}, C = {C}")
+    for t in acts:
+        assert t.dtype == torch.bfloat16, f"{name}: activations are bf16"
+        assert t.is_contiguous(), f"{name}: activations are contiguous"
+        assert t.shape == x.shape, (t.shape, x.shape)
+        assert t.data_ptr() % 16 == 0, "16-byte lanes need an aligned tensor"
+    for p in params:
+        if p is not None:
+            assert p.dtype == torch.float32 and p.is_contiguous()
+            assert p.numel() == C, (p.shape, C)
+    for t in (*acts, *params):
+        assert t is None or (t.is_cuda and t.device == x.device)
+    return M, C
+
+
+def _ptr(t: tp.Optional[torch.Tensor]) -> int:
+    return t.data_ptr() if t is not None else 0
+
+
+def _ln_ws(M: int, C: int, k: int, like: torch.Tensor) -> torch.Tensor:
+    return torch.empty(require().ln_plan(M, C)[5], k, C, dtype=torch.float32,
+                       device=like.device)
+
+
+def ln_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+           y: torch.Tensor, stats: torch.Tensor, eps: float,
+           b_in: tp.Optional[torch.Tensor] = None) -> None:
+    """y = (x + b_in - mean) * rstd * gamma + beta over the last dim, two-pass
+    statistics; ``stats`` (fp32 [M, 2]) receives each row's (mean, rstd)."""
+    M, C = _ln_check("ln_fwd", True, [x, y], [gamma, beta, b_in])
+    assert stats.dtype == torch.float32 and stats.is_contiguous()
+    assert stats.numel() == 2 * M and stats.device == x.device
+    require().ln_fwd(x.data_ptr(), _ptr(b_in), gamma.data_ptr(),
+                     beta.data_ptr(), y.data_ptr(), stats.data_ptr(), M, C,
+                     float(eps), _stream())
+
+
+def ln_bwd(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor,
+           gamma: torch.Tensor, dx: tp.Optional[torch.Tensor],
+           dgamma: tp.Optional[torch.Tensor],
+           dbeta: tp.Optional[torch.Tensor],
+           b_in: tp.Optional[torch.Tensor] = None,
+           db_in: tp.Optional[torch.Tensor] = None) -> None:
+    """Backward of :func:`ln_fwd` from its input and saved ``stats``: writes
+    ``dx`` (unless None) and adds sum dy * xhat, sum dy and, with ``b_in``,
+    sum dx (before its rounding) into ``dgamma`` / ``dbeta`` / ``db_in``.
+    Deterministic: no atomics."""
+    M, C = _ln_check("ln_bwd", True, [dy, x] + ([dx] if dx is not None else []),
+                     [gamma, b_in, dgamma, dbeta, db_in])
+    assert stats.dtype == torch.float32 and stats.is_contiguous()
+    assert stats.numel() == 2 * M and stats.device == x.device
+    assert db_in is None or b_in is not None
+    ws = _ln_ws(M, C, 3 if b_in is not None else 2, x)
+    require().ln_bwd(dy.data_ptr(), x.data_ptr(), _ptr(b_in),
+                     stats.data_ptr(), gamma.data_ptr(), _ptr(dx),
+                     ws.data_ptr(), _ptr(dgamma), _ptr(dbeta), _ptr(db_in),
+                     M, C, _stream())
+
+
+def bias_gelu_fwd(h: torch.Tensor, b: torch.Tensor, g: torch.Tensor) -> None:
+    """g = gelu(h + b), the erf form 0.5 u (1 + erf(u / sqrt 2))."""
+    M, C = _ln_check("bias_gelu_fwd", False, [h, g], [b])
+    require().bias_gelu_fwd(h.data_ptr(), b.data_ptr(), g.data_ptr(), M, C,
+                            _stream())
+
+
+def bias_gelu_bwd(dg: torch.Tensor, h: torch.Tensor, b: torch.Tensor,
+                  dh: torch.Tensor, db: tp.Optional[torch.Tensor]) -> None:
+    """dh = dg * gelu'(h + b), recomputed from ``h``; ``db`` += sum dh."""
+    M, C = _ln_check("bias_gelu_bwd", False, [dg, h, dh], [b, db])
+    ws = _ln_ws(M, C, 1, h)
+    require().bias_gelu_bwd(dg.data_ptr(), h.data_ptr(), b.data_ptr(),
+                            dh.data_ptr(), ws.data_ptr(), _ptr(db), M, C,
+                            _stream())
+
+
+def scale_residual_fwd(z: torch.Tensor, b: torch.Tensor, s: torch.Tensor,
+                       res: torch.Tensor, out: torch.Tensor) -> None:
+    """out = res + s * (z + b), ``s`` the per-channel layer scale."""
+    M, C = _ln_check("scale_residual_fwd", False, [z, res, out], [b, s])
+    require().scale_residual_fwd(z.data_ptr(), b.data_ptr(), s.data_ptr(),
+                                 res.data_ptr(), out.data_ptr(), M, C,
+                                 _stream())
+
+
+def scale_residual_bwd(dout: torch.Tensor, z: torch.Tensor, b: torch.Tensor,
+                       s: torch.Tensor, dz: torch.Tensor,
+                       ds: tp.Optional[torch.Tensor],
+                       db: tp.Optional[torch.Tensor]) -> None:
+    """dz = s * dout; ``ds`` += sum dout * (z + b), ``db`` += sum s * dout.
+    The residual branch's gradient is ``dout`` itself: nothing is copied."""
+    M, C = _ln_check("scale_residual_bwd", False, [dout, z, dz], [b, s, ds, db])
+    ws = _ln_ws(M, C, 2, z)
+    require().scale_residual_bwd(dout.data_ptr(), z.data_ptr(), b.data_ptr(),
+                                 s.data_ptr(), dz.data_ptr(), ws.data_ptr(),
+                                 _ptr(ds), _ptr(db), M, C, _stream())
+
+
+# ---------------------------------------------------------------------------
 # batchnorm kernels (NHWC training BN; see flashy_amd/nn.py)
 # ---------------------------------------------------------------------------
 

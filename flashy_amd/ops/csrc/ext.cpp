@@ -74,6 +74,25 @@ int launch_dwconv_dgrad(const void* dy, const void* w16, void* dx, ConvDims d,
                         hipStream_t stream);
 int launch_dwconv_wgrad(const void* x, const void* dy, void* ws, void* dw,
                         ConvDims d, hipStream_t stream);
+int ln_plan(int M, int C, int* out);
+int launch_ln_fwd(const void* x, const void* b_in, const void* gamma,
+                  const void* beta, void* y, void* stats, int M, int C,
+                  float eps, hipStream_t stream);
+int launch_ln_bwd(const void* dy, const void* x, const void* b_in,
+                  const void* stats, const void* gamma, void* dx, void* ws,
+                  void* dgamma, void* dbeta, void* db_in, int M, int C,
+                  hipStream_t stream);
+int launch_bias_gelu_fwd(const void* h, const void* b, void* out, int M, int C,
+                         hipStream_t stream);
+int launch_bias_gelu_bwd(const void* dg, const void* h, const void* b,
+                         void* dh, void* ws, void* db, int M, int C,
+                         hipStream_t stream);
+int launch_scale_residual_fwd(const void* z, const void* b, const void* s,
+                              const void* res, void* out, int M, int C,
+                              hipStream_t stream);
+int launch_scale_residual_bwd(const void* dout, const void* z, const void* b,
+                              const void* s, void* dz, void* ws, void* ds,
+                              void* db, int M, int C, hipStream_t stream);
 void launch_bn_stats(const void* x, void* partials, int64_t M, int C,
                      int msplit, hipStream_t stream);
 void launch_bn_finalize(const void* partials, int msplit, const void* gamma,
@@ -496,6 +515,79 @@ PYBIND11_MODULE(_hip_ops, m) {
                       make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
                       as_stream(stream)))
                   throw std::invalid_argument("dwconv_wgrad: unsupported shape");
+              check_last();
+          });
+    // LayerNorm / bias+GELU / layer scale (csrc/layernorm.hip): the plan's
+    // (served, lanes per row, rows per block, grid, column chunks, column-sum
+    // slices); a 0 pointer is an absent operand or a gradient nobody wants
+    m.def("ln_plan", [](int M, int C) {
+        int p[5];
+        const int served = ln_plan(M, C, p);
+        return py::make_tuple(served, p[0], p[1], p[2], p[3], p[4]);
+    });
+    m.def("ln_fwd",
+          [](uintptr_t x, uintptr_t b_in, uintptr_t gamma, uintptr_t beta,
+             uintptr_t y, uintptr_t stats, int M, int C, float eps,
+             uintptr_t stream) {
+              if (!launch_ln_fwd((const void*)x, (const void*)b_in,
+                                 (const void*)gamma, (const void*)beta,
+                                 (void*)y, (void*)stats, M, C, eps,
+                                 as_stream(stream)))
+                  throw std::invalid_argument("ln_fwd: unsupported shape");
+              check_last();
+          });
+    m.def("ln_bwd",
+          [](uintptr_t dy, uintptr_t x, uintptr_t b_in, uintptr_t stats,
+             uintptr_t gamma, uintptr_t dx, uintptr_t ws, uintptr_t dgamma,
+             uintptr_t dbeta, uintptr_t db_in, int M, int C,
+             uintptr_t stream) {
+              if (!launch_ln_bwd((const void*)dy, (const void*)x,
+                                 (const void*)b_in, (const void*)stats,
+                                 (const void*)gamma, (void*)dx, (void*)ws,
+                                 (void*)dgamma, (void*)dbeta, (void*)db_in, M,
+                                 C, as_stream(stream)))
+                  throw std::invalid_argument("ln_bwd: unsupported shape");
+              check_last();
+          });
+    m.def("bias_gelu_fwd",
+          [](uintptr_t h, uintptr_t b, uintptr_t out, int M, int C,
+             uintptr_t stream) {
+              if (!launch_bias_gelu_fwd((const void*)h, (const void*)b,
+                                        (void*)out, M, C, as_stream(stream)))
+                  throw std::invalid_argument("bias_gelu_fwd: unsupported shape");
+              check_last();
+          });
+    m.def("bias_gelu_bwd",
+          [](uintptr_t dg, uintptr_t h, uintptr_t b, uintptr_t dh,
+             uintptr_t ws, uintptr_t db, int M, int C, uintptr_t stream) {
+              if (!launch_bias_gelu_bwd((const void*)dg, (const void*)h,
+                                        (const void*)b, (void*)dh, (void*)ws,
+                                        (void*)db, M, C, as_stream(stream)))
+                  throw std::invalid_argument("bias_gelu_bwd: unsupported shape");
+              check_last();
+          });
+    m.def("scale_residual_fwd",
+          [](uintptr_t z, uintptr_t b, uintptr_t s, uintptr_t res,
+             uintptr_t out, int M, int C, uintptr_t stream) {
+              if (!launch_scale_residual_fwd((const void*)z, (const void*)b,
+                                             (const void*)s, (const void*)res,
+                                             (void*)out, M, C,
+                                             as_stream(stream)))
+                  throw std::invalid_argument(
+                      "scale_residual_fwd: unsupported shape");
+              check_last();
+          });
+    m.def("scale_residual_bwd",
+          [](uintptr_t dout, uintptr_t z, uintptr_t b, uintptr_t s,
+             uintptr_t dz, uintptr_t ws, uintptr_t ds, uintptr_t db, int M,
+             int C, uintptr_t stream) {
+              if (!launch_scale_residual_bwd((const void*)dout, (const void*)z,
+                                             (const void*)b, (const void*)s,
+                                             (void*)dz, (void*)ws, (void*)ds,
+                                             (void*)db, M, C,
+                                             as_stream(stream)))
+                  throw std::invalid_argument(
+                      "scale_residual_bwd: unsupported shape");
               check_last();
           });
     m.def("bn_stats",
