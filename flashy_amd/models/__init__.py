@@ -11,8 +11,9 @@ from .resnet import (ResNet, resnet18, resnet50,  # noqa: F401
                      resnext50_32x4d)
 from .resnet_native import (NativeResNet, native_resnet18,  # noqa: F401
                             native_resnet50, native_resnext50_32x4d)
-from .convnext import ConvNeXtBlock  # noqa: F401
-from .convnext_native import NativeConvNeXtBlock  # noqa: F401
+from .convnext import ConvNeXt, ConvNeXtBlock  # noqa: F401
+from .convnext_native import (NativeConvNeXt,  # noqa: F401
+                              NativeConvNeXtBlock)
 from .dcgan import DCGANGenerator, DCGANDiscriminator  # noqa: F401
 from .dcgan_native import (NativeDCGANGenerator,  # noqa: F401
                            NativeDCGANDiscriminator)

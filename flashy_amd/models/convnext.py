@@ -1,12 +1,15 @@
 # Copyright (c) Flashy-AMD authors.
-"""ConvNeXt block (Liu et al., "A ConvNet for the 2020s"), plain torch: the
-twin of :mod:`flashy_amd.models.convnext_native`, as resnet.py is of
-resnet_native.py.  Only the block: see TODO.md for the rest of the network.
+"""ConvNeXt (Liu et al., "A ConvNet for the 2020s"), plain torch: the twin of
+:mod:`flashy_amd.models.convnext_native`, as resnet.py is of
+resnet_native.py.  No stochastic depth (TODO.md).
 """
 from __future__ import annotations
 
+import typing as tp
+
 import torch
 from torch import nn
+import torch.nn.functional as F
 
 
 class ConvNeXtBlock(nn.Module):
@@ -29,3 +32,43 @@ class ConvNeXtBlock(nn.Module):
         y = self.dwconv(x).permute(0, 2, 3, 1)
         y = self.pwconv2(self.act(self.pwconv1(self.norm(y))))
         return x + (self.gamma * y).permute(0, 3, 1, 2)
+
+
+class ChannelLayerNorm(nn.LayerNorm):
+    """LayerNorm over the channels of an NCHW tensor."""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        y = F.layer_norm(x.permute(0, 2, 3, 1), self.normalized_shape,
+                         self.weight, self.bias, self.eps)
+        return y.permute(0, 3, 1, 2)
+
+
+class ConvNeXt(nn.Module):
+    """NCHW in, logits out: patchify stem (conv ``patch`` x ``patch`` stride
+    ``patch`` with bias, channel LayerNorm), four stages of
+    :class:`ConvNeXtBlock` with LayerNorm + conv 2x2 stride 2 between them,
+    global mean, LayerNorm, Linear."""
+
+    def __init__(self, depths: tp.Sequence[int], dims: tp.Sequence[int],
+                 num_classes: int, patch: int = 4, in_chans: int = 3):
+        super().__init__()
+        assert len(depths) == len(dims) == 4, (depths, dims)
+        self.stem = nn.Conv2d(in_chans, dims[0], patch, patch)
+        self.stem_norm = ChannelLayerNorm(dims[0], eps=1e-6)
+        self.stages = nn.ModuleList(
+            nn.Sequential(*[ConvNeXtBlock(d) for _ in range(n)])
+            for n, d in zip(depths, dims))
+        self.down_norms = nn.ModuleList(
+            ChannelLayerNorm(d, eps=1e-6) for d in dims[:3])
+        self.down_convs = nn.ModuleList(
+            nn.Conv2d(d, d2, 2, 2) for d, d2 in zip(dims[:3], dims[1:]))
+        self.head_norm = nn.LayerNorm(dims[3], eps=1e-6)
+        self.fc = nn.Linear(dims[3], num_classes)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = self.stem_norm(self.stem(x))
+        for i, stage in enumerate(self.stages):
+            if i:
+                x = self.down_convs[i - 1](self.down_norms[i - 1](x))
+            x = stage(x)
+        return self.fc(self.head_norm(x.mean(dim=(2, 3))))

@@ -11,11 +11,13 @@ depthwise [C,1,k,k] -> [C,k,k,1], Linear [O,I] -> 1x1 conv [O,1,1,I].
 """
 from __future__ import annotations
 
+import typing as tp
+
 import torch
 from torch import nn
 
 from .. import nn as fnn
-from .convnext import ConvNeXtBlock
+from .convnext import ConvNeXt, ConvNeXtBlock
 
 
 class NativeConvNeXtBlock(nn.Module):
@@ -60,3 +62,77 @@ class NativeConvNeXtBlock(nn.Module):
         block.pwconv2_bias.copy_(twin.pwconv2.bias)
         block.gamma.copy_(twin.gamma)
         return block
+
+
+class NativeConvNeXt(nn.Module):
+    """The whole network, NHWC bf16 ``[N, H, W, in_chans]`` in, fp32 logits
+    out.  Stem: the patch conv kernels (csrc/conv_patch.hip), its bias folded
+    into the LayerNorm behind it.  Downsample: LayerNorm, the dense 2x2
+    stride-2 conv, :func:`flashy_amd.nn.bias_add`.  Head: the pooling
+    kernels, LayerNorm on ``[N, 1, 1, C]``, :class:`flashy_amd.nn.Linear`.
+    Every ``dims[i] % 64 == 0``, as the block demands."""
+
+    def __init__(self, depths: tp.Sequence[int], dims: tp.Sequence[int],
+                 num_classes: int, patch: int = 4, in_chans: int = 3):
+        super().__init__()
+        if len(depths) != 4 or len(dims) != 4 or \
+                any(d < 64 or d % 64 for d in dims):
+            raise ValueError(
+                f"NativeConvNeXt needs four stages with dims % 64 == 0 (the "
+                f"dense conv kernels), got depths={depths} dims={dims}")
+        self.stem = fnn.Conv2d(in_chans, dims[0], patch, patch, 0,
+                               input_grad=False)
+        if not self.stem.patch:
+            raise ValueError(
+                f"NativeConvNeXt stem: {fnn.ops.PATCHCONV_RULE}; got "
+                f"patch={patch} in_chans={in_chans} dims[0]={dims[0]}")
+        self.stem_bias = nn.Parameter(torch.zeros(dims[0]))
+        self.stem_norm = fnn.LayerNorm2d(dims[0], eps=1e-6)
+        self.stages = nn.ModuleList(
+            nn.Sequential(*[NativeConvNeXtBlock(d) for _ in range(n)])
+            for n, d in zip(depths, dims))
+        self.down_norms = nn.ModuleList(
+            fnn.LayerNorm2d(d, eps=1e-6) for d in dims[:3])
+        self.down_convs = nn.ModuleList(
+            fnn.Conv2d(d, d2, 2, 2, 0) for d, d2 in zip(dims[:3], dims[1:]))
+        self.down_biases = nn.ParameterList(
+            nn.Parameter(torch.zeros(d2)) for d2 in dims[1:])
+        self.head_norm = fnn.LayerNorm2d(dims[3], eps=1e-6)
+        self.fc = fnn.Linear(dims[3], num_classes)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = self.stem_norm(self.stem(x), self.stem_bias)
+        for i, stage in enumerate(self.stages):
+            if i:
+                x = fnn.bias_add(self.down_convs[i - 1](self.down_norms[i - 1](x)),
+                                 self.down_biases[i - 1])
+            x = stage(x)
+        pooled = fnn.global_avg_pool(x)                     # fp32 [N, C]
+        n, c = pooled.shape
+        y = self.head_norm(pooled.to(torch.bfloat16).view(n, 1, 1, c))
+        return self.fc(y.view(n, c).float())
+
+    @classmethod
+    @torch.no_grad()
+    def from_torch(cls, twin: ConvNeXt) -> "NativeConvNeXt":
+        depths = [len(s) for s in twin.stages]
+        dims = [s[0].gamma.numel() if len(s) else c.out_channels
+                for s, c in zip(twin.stages, [twin.stem, *twin.down_convs])]
+        net = cls(depths, dims, twin.fc.out_features,
+                  twin.stem.kernel_size[0], twin.stem.in_channels)
+        net.stem.weight.copy_(twin.stem.weight.permute(0, 2, 3, 1))
+        net.stem_bias.copy_(twin.stem.bias)
+        for mine, theirs in [(net.stem_norm, twin.stem_norm),
+                             (net.head_norm, twin.head_norm),
+                             (net.fc, twin.fc),
+                             *zip(net.down_norms, twin.down_norms)]:
+            mine.weight.copy_(theirs.weight)
+            mine.bias.copy_(theirs.bias)
+        for conv, bias, theirs in zip(net.down_convs, net.down_biases,
+                                      twin.down_convs):
+            conv.weight.copy_(theirs.weight.permute(0, 2, 3, 1))
+            bias.copy_(theirs.bias)
+        net.stages = nn.ModuleList(
+            nn.Sequential(*[NativeConvNeXtBlock.from_torch(b) for b in s])
+            for s in twin.stages)
+        return net

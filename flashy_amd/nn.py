@@ -171,8 +171,47 @@ class _DepthwiseConvFn(torch.autograd.Function):
                 None, None, None)
 
 
+class _PatchConvFn(torch.autograd.Function):
+    """Patch conv, kernel == stride, pad 0, 3 or 4 input channels
+    (csrc/conv_patch.hip), weight [K, p, p, C]; backward-data reads the same
+    KRSC weight.  Emits no BatchNorm partials, as the grouped path."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, w: torch.Tensor, stride: int,
+                input_grad: bool):
+        w16 = _weight_bf16(w).contiguous()
+        x = x.contiguous()
+        d = ops.ConvDims.infer(x, w16, stride, 0)
+        y = x.new_empty((d.N, d.Ho, d.Wo, d.K))
+        ops.patchconv_fwd(x, w16, y, d)
+        ctx.save_for_backward(x, w16)
+        ctx.dims = d
+        ctx.input_grad = input_grad
+        ctx.w_ref = w
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        x, w16 = ctx.saved_tensors
+        d: ops.ConvDims = ctx.dims
+        dy = dy.contiguous()
+        dw_buf = None
+        direct = True
+        if ctx.needs_input_grad[1]:  # skip wgrad entirely for frozen weights
+            dw_buf, direct = _grad_target(ctx.w_ref)
+            ops.patchconv_wgrad(x, dy, dw_buf, d)
+        dx = None
+        if ctx.input_grad:
+            dx = x.new_empty(x.shape)
+            ops.patchconv_dgrad(dy, w16, dx, d)
+        return (dx, dw_buf if dw_buf is not None and not direct else None,
+                None, None)
+
+
 class Conv2d(nn.Module):
     """NHWC bf16 conv (no bias, as in ResNet).  Weight: [K, R, S, C] fp32;
+    a patch conv (kernel == stride, no padding, 3 or 4 input channels:
+    :func:`flashy_amd.ops.patchconv_supported`) runs the patch kernels;
     with ``groups > 1`` a grouped 3x3 conv with weight [K, 3, 3, C // groups]
     (the shapes :func:`flashy_amd.ops.gconv_supported` accepts), or, with
     ``groups == in_channels == out_channels``, a depthwise k x k conv with
@@ -193,13 +232,16 @@ class Conv2d(nn.Module):
         self._wt_view: tp.Optional[torch.Tensor] = None
         k = kernel_size
         self.depthwise = groups != 1 and groups == in_channels == out_channels
+        # the plans are dims-only and ignore the image size: probe 8x8
+        probe = ops.ConvDims(1, 8, 8, in_channels, out_channels, k, k,
+                             (8 + 2 * padding - k) // stride + 1
+                             if stride > 0 else 0,
+                             (8 + 2 * padding - k) // stride + 1
+                             if stride > 0 else 0, stride, padding)
+        # the cheap part of the rule first: most convs never ask the plan
+        self.patch = groups == 1 and k == stride and padding == 0 \
+            and in_channels <= 4 and ops.patchconv_supported(probe)
         if groups != 1:
-            # the plan is dims-only and ignores the image size: probe 8x8
-            probe = ops.ConvDims(1, 8, 8, in_channels, out_channels, k, k,
-                                 (8 + 2 * padding - k) // stride + 1
-                                 if stride > 0 else 0,
-                                 (8 + 2 * padding - k) // stride + 1
-                                 if stride > 0 else 0, stride, padding)
             if self.depthwise:
                 if not ops.dwconv_supported(probe):
                     raise ValueError(
@@ -226,6 +268,9 @@ class Conv2d(nn.Module):
             return _GroupedConvFn.apply(x, self.weight, self.stride,
                                         self.padding, self.groups,
                                         self.input_grad and x.requires_grad)
+        if self.patch:
+            return _PatchConvFn.apply(x, self.weight, self.stride,
+                                      self.input_grad and x.requires_grad)
         return _ConvFn.apply(x, self.weight, self.stride, self.padding,
                              self.input_grad and x.requires_grad,
                              self._wt_view, self.feeds_bn and self.training)
@@ -780,6 +825,36 @@ def bias_gelu(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """``gelu(x + bias)`` (erf form) over NHWC bf16 ``x`` with an fp32
     per-channel ``bias``, one launch; backward recomputes from ``x``."""
     return _BiasGeluFn.apply(x, bias)
+
+
+class _BiasAddFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z: torch.Tensor, bias: torch.Tensor):
+        ops.bias_add(z, bias)
+        ctx.mark_dirty(z)
+        ctx.refs = (bias,)
+        return z
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        (bias,) = ctx.refs
+        (db,), grads = _param_grads(ctx, (bias,), 1)
+        if db is not None:
+            ops.bias_add_bwd(dout.contiguous(), db)
+        return (dout, *grads)
+
+
+def bias_add(z: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """``z + bias`` over contiguous NHWC bf16 ``z`` with an fp32 per-channel
+    ``bias``, one launch, IN PLACE on ``z`` (the conv that produced it does
+    not save its output); the input gradient is the output's, unchanged."""
+    return _BiasAddFn.apply(z, bias)
+
+
+def global_avg_pool(x: torch.Tensor) -> torch.Tensor:
+    """Mean over H and W of an NHWC bf16 tensor: fp32 ``[N, C]`` (the
+    pooling kernels of the classifier head, csrc/head.hip)."""
+    return _PoolFn.apply(x)
 
 
 class _ScaleResidualFn(torch.autograd.Function):

@@ -1043,6 +1043,72 @@ def dwconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# patch convolution (csrc/conv_patch.hip): kernel == stride, no padding, 3 or
+# 4 input channels.  Weights are [K, p, p, C] and are read as they are.
+# ---------------------------------------------------------------------------
+
+PATCHCONV_RULE = ("patch conv needs a square kernel equal to the stride, 2 or "
+                  "4, padding 0, 3 or 4 input channels, out_channels % 16 == 0 "
+                  "and 16 <= out_channels <= 512")
+
+
+def patchconv_supported(d: ConvDims) -> bool:
+    """Whether the patch kernels serve ``d`` (dims only; the plan lives in
+    conv_patch.hip)."""
+    return require().patchconv_plan(*d)[0] > 0
+
+
+def _patchconv_check(d: ConvDims, w: torch.Tensor, w_dtype,
+                     acts: tp.Sequence[tp.Tuple[torch.Tensor,
+                                                tp.Tuple[int, ...]]]) -> int:
+    ok, splits = require().patchconv_plan(*d)
+    if not ok:
+        raise ValueError(
+            f"{PATCHCONV_RULE}, N >= 1, H, W >= kernel and Ho, Wo = "
+            f"H // kernel, W // kernel; got {d}")
+    assert w.dtype == w_dtype and w.is_cuda and w.is_contiguous()
+    assert tuple(w.shape) == (d.K, d.R, d.S, d.C), (w.shape, d)
+    for t, shape in acts:
+        assert t.dtype == torch.bfloat16 and t.is_cuda and t.is_contiguous()
+        assert tuple(t.shape) == shape, (t.shape, shape)
+        assert t.data_ptr() % 16 == 0, "16-byte lanes need an aligned tensor"
+    return splits
+
+
+def patchconv_fwd(x: torch.Tensor, w16: torch.Tensor, y: torch.Tensor,
+                  d: ConvDims) -> None:
+    """y[N, H // p, W // p, K] = patch conv of x[N, H, W, C] with the bf16
+    weights ``w16`` [K, p, p, C]."""
+    _patchconv_check(d, w16, torch.bfloat16, [(x, (d.N, d.H, d.W, d.C)),
+                                              (y, (d.N, d.Ho, d.Wo, d.K))])
+    require().patchconv_fwd(x.data_ptr(), w16.data_ptr(), y.data_ptr(), *d,
+                            _stream())
+
+
+def patchconv_dgrad(dy: torch.Tensor, w16: torch.Tensor, dx: torch.Tensor,
+                    d: ConvDims) -> None:
+    """dx[N, H, W, C] from dy[N, Ho, Wo, K]; every element of dx is written,
+    the rows and columns no patch covers with zeros."""
+    _patchconv_check(d, w16, torch.bfloat16, [(dy, (d.N, d.Ho, d.Wo, d.K)),
+                                              (dx, (d.N, d.H, d.W, d.C))])
+    require().patchconv_dgrad(dy.data_ptr(), w16.data_ptr(), dx.data_ptr(),
+                              *d, _stream())
+
+
+def patchconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor,
+                    d: ConvDims) -> None:
+    """Accumulates (+=) the fp32 weight gradient [K, p, p, C] into ``dw``.
+    The m-splits write fp32 slices that a combine kernel sums in split
+    order: no atomics, bitwise repeatable."""
+    splits = _patchconv_check(d, dw, torch.float32,
+                              [(x, (d.N, d.H, d.W, d.C)),
+                               (dy, (d.N, d.Ho, d.Wo, d.K))])
+    ws = torch.empty(splits, dw.numel(), dtype=torch.float32, device=x.device)
+    require().patchconv_wgrad(x.data_ptr(), dy.data_ptr(), ws.data_ptr(),
+                              dw.data_ptr(), *d, _stream())
+
+
+# ---------------------------------------------------------------------------
 # channel LayerNorm, bias+GELU, layer scale + residual (csrc/layernorm.hip).
 # Activations are contiguous bf16 [..., C] (NHWC: M = the product of the
 # leading dims); parameters and their gradients are fp32 [C].  Gradient
@@ -1155,6 +1221,21 @@ def bias_gelu_bwd(dg: torch.Tensor, h: torch.Tensor, b: torch.Tensor,
     require().bias_gelu_bwd(dg.data_ptr(), h.data_ptr(), b.data_ptr(),
                             dh.data_ptr(), ws.data_ptr(), _ptr(db), M, C,
                             _stream())
+
+
+def bias_add(z: torch.Tensor, b: torch.Tensor) -> None:
+    """z = bf16(z + b), in place."""
+    M, C = _ln_check("bias_add", False, [z], [b])
+    require().bias_add(z.data_ptr(), b.data_ptr(), M, C, _stream())
+
+
+def bias_add_bwd(dout: torch.Tensor, db: tp.Optional[torch.Tensor]) -> None:
+    """``db`` += the column sums of ``dout`` (the input gradient of
+    :func:`bias_add` is ``dout`` itself)."""
+    M, C = _ln_check("bias_add_bwd", False, [dout], [db])
+    ws = _ln_ws(M, C, 1, dout)
+    require().bias_add_bwd(dout.data_ptr(), ws.data_ptr(), _ptr(db), M, C,
+                           _stream())
 
 
 def scale_residual_fwd(z: torch.Tensor, b: torch.Tensor, s: torch.Tensor,

@@ -74,6 +74,16 @@ int launch_dwconv_dgrad(const void* dy, const void* w16, void* dx, ConvDims d,
                         hipStream_t stream);
 int launch_dwconv_wgrad(const void* x, const void* dy, void* ws, void* dw,
                         ConvDims d, hipStream_t stream);
+int patchconv_plan(ConvDims d, int* wgrad_splits);
+int launch_patchconv_fwd(const void* x, const void* w16, void* y, ConvDims d,
+                         hipStream_t stream);
+int launch_patchconv_dgrad(const void* dy, const void* w16, void* dx,
+                           ConvDims d, hipStream_t stream);
+int launch_patchconv_wgrad(const void* x, const void* dy, void* ws, void* dw,
+                           ConvDims d, hipStream_t stream);
+int launch_bias_add(void* z, const void* b, int M, int C, hipStream_t stream);
+int launch_bias_add_bwd(const void* dout, void* ws, void* db, int M, int C,
+                        hipStream_t stream);
 int ln_plan(int M, int C, int* out);
 int launch_ln_fwd(const void* x, const void* b_in, const void* gamma,
                   const void* beta, void* y, void* stats, int M, int C,
@@ -515,6 +525,66 @@ PYBIND11_MODULE(_hip_ops, m) {
                       make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
                       as_stream(stream)))
                   throw std::invalid_argument("dwconv_wgrad: unsupported shape");
+              check_last();
+          });
+    // patch conv (csrc/conv_patch.hip): the plan's (served, wgrad splits);
+    // the launchers read the bf16 weights [K][p][p][C] as they are
+    m.def("patchconv_plan",
+          [](int N, int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad) {
+              int splits = 0;
+              const int ok = patchconv_plan(
+                  make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad), &splits);
+              return py::make_tuple(ok, splits);
+          });
+    m.def("patchconv_fwd",
+          [](uintptr_t x, uintptr_t w16, uintptr_t y, int N, int H, int W,
+             int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
+             uintptr_t stream) {
+              if (!launch_patchconv_fwd(
+                      (const void*)x, (const void*)w16, (void*)y,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      as_stream(stream)))
+                  throw std::invalid_argument("patchconv_fwd: unsupported shape");
+              check_last();
+          });
+    m.def("patchconv_dgrad",
+          [](uintptr_t dy, uintptr_t w16, uintptr_t dx, int N, int H, int W,
+             int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
+             uintptr_t stream) {
+              if (!launch_patchconv_dgrad(
+                      (const void*)dy, (const void*)w16, (void*)dx,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      as_stream(stream)))
+                  throw std::invalid_argument(
+                      "patchconv_dgrad: unsupported shape");
+              check_last();
+          });
+    m.def("patchconv_wgrad",
+          [](uintptr_t x, uintptr_t dy, uintptr_t ws, uintptr_t dw, int N,
+             int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad, uintptr_t stream) {
+              if (!launch_patchconv_wgrad(
+                      (const void*)x, (const void*)dy, (void*)ws, (void*)dw,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      as_stream(stream)))
+                  throw std::invalid_argument(
+                      "patchconv_wgrad: unsupported shape");
+              check_last();
+          });
+    m.def("bias_add",
+          [](uintptr_t z, uintptr_t b, int M, int C, uintptr_t stream) {
+              if (!launch_bias_add((void*)z, (const void*)b, M, C,
+                                   as_stream(stream)))
+                  throw std::invalid_argument("bias_add: unsupported shape");
+              check_last();
+          });
+    m.def("bias_add_bwd",
+          [](uintptr_t dout, uintptr_t ws, uintptr_t db, int M, int C,
+             uintptr_t stream) {
+              if (!launch_bias_add_bwd((const void*)dout, (void*)ws, (void*)db,
+                                       M, C, as_stream(stream)))
+                  throw std::invalid_argument("bias_add_bwd: unsupported shape");
               check_last();
           });
     // LayerNorm / bias+GELU / layer scale (csrc/layernorm.hip): the plan's

@@ -516,6 +516,43 @@ k_scale_residual_bwd(const uint16_t* __restrict__ dout,
     ln_fold<1>(red, a_b, slice + g.C, w, g);
 }
 
+// z = bf16(z + b), in place
+__global__ void __launch_bounds__(LN_THREADS)
+k_bias_add(uint16_t* z, const float* __restrict__ b, LnGeom g) {
+    LnWalk<1> w(g);
+    float bi[8];
+    ln_param8(b, w.ch[0], w.on[0], 0.f, bi);
+    if (!w.on[0]) return;
+    for (int row = w.row; row < w.rend; row += w.RB) {
+        const int64_t at = (int64_t)row * g.C + w.ch[0];
+        float f[8];
+        ln_load8(z, at, f);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) f[c] += bi[c];
+        ln_store8(z, at, f);
+    }
+}
+
+// slice sum: dout (the gradient of a per-channel bias; dz is dout itself)
+__global__ void __launch_bounds__(LN_THREADS)
+k_bias_add_bwd(const uint16_t* __restrict__ dout, float* __restrict__ ws,
+               LnGeom g) {
+    __shared__ float red[LN_THREADS * 8];
+    LnWalk<1> w(g);
+    float a_b[1][8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) a_b[0][c] = 0.f;
+    if (w.on[0]) {
+        for (int row = w.row; row < w.rend; row += w.RB) {
+            float d[8];
+            ln_load8(dout, (int64_t)row * g.C + w.ch[0], d);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) a_b[0][c] += d[c];
+        }
+    }
+    ln_fold<1>(red, a_b, ws + (int64_t)blockIdx.x * g.C, w, g);
+}
+
 // ws: fp32 [slices][k][C].  d_j[c] += sum over the slices of ws[.][j][c] for
 // every non-null d_j: 8 contiguous runs of slices, each in slice order, then
 // the run totals in run order.  A block serves LN_RCOLS of the k * C columns.
@@ -635,6 +672,26 @@ extern "C" int launch_scale_residual_fwd(const void* z, const void* b,
     k_scale_residual_fwd<<<grid, LN_THREADS, 0, stream>>>(
         (const uint16_t*)z, (const float*)b, (const float*)s,
         (const uint16_t*)res, (uint16_t*)out, g);
+    return 1;
+}
+
+extern "C" int launch_bias_add(void* z, const void* b, int M, int C,
+                               hipStream_t stream) {
+    LnGeom g; dim3 grid; int slices;
+    if (!ln_geom(M, C, false, &g, &grid, &slices)) return 0;
+    k_bias_add<<<grid, LN_THREADS, 0, stream>>>((uint16_t*)z, (const float*)b,
+                                                g);
+    return 1;
+}
+
+// k = 1; db += the column sums of dout
+extern "C" int launch_bias_add_bwd(const void* dout, void* ws, void* db, int M,
+                                   int C, hipStream_t stream) {
+    LnGeom g; dim3 grid; int slices;
+    if (!ln_geom(M, C, false, &g, &grid, &slices)) return 0;
+    k_bias_add_bwd<<<grid, LN_THREADS, 0, stream>>>((const uint16_t*)dout,
+                                                    (float*)ws, g);
+    ln_combine(ws, db, nullptr, nullptr, 1, C, slices, stream);
     return 1;
 }
 
