@@ -6,14 +6,23 @@ The reference has no model zoo (it borrows torchvision's resnet18,
 here, so the architectures the benchmark configs name are implemented
 in-house: ResNet-18/50 (CIFAR and ImageNet stems) and the DCGAN-style 64x64
 generator/discriminator pair used by the adversarial workload.
+
+ConvNeXt comes as a torch twin and a native network: ``ConvNeXt`` /
+``NativeConvNeXt`` with ``convnext_tiny`` / ``convnext_small`` and
+``native_convnext_tiny`` / ``native_convnext_small`` (depths (3, 3, 9, 3) /
+(3, 3, 27, 3), dims (96, 192, 384, 768)).  The native classes take
+``dense_only=False`` for widths off the 64 grid, which the pointwise conv
+kernels serve; the native constructors pass it.
 """
 from .resnet import (ResNet, resnet18, resnet50,  # noqa: F401
                      resnext50_32x4d)
 from .resnet_native import (NativeResNet, native_resnet18,  # noqa: F401
                             native_resnet50, native_resnext50_32x4d)
-from .convnext import ConvNeXt, ConvNeXtBlock  # noqa: F401
+from .convnext import (ConvNeXt, ConvNeXtBlock,  # noqa: F401
+                       convnext_small, convnext_tiny)
 from .convnext_native import (NativeConvNeXt,  # noqa: F401
-                              NativeConvNeXtBlock)
+                              NativeConvNeXtBlock, native_convnext_small,
+                              native_convnext_tiny)
 from .dcgan import DCGANGenerator, DCGANDiscriminator  # noqa: F401
 from .dcgan_native import (NativeDCGANGenerator,  # noqa: F401
                            NativeDCGANDiscriminator)

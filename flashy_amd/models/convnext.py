@@ -72,3 +72,11 @@ class ConvNeXt(nn.Module):
                 x = self.down_convs[i - 1](self.down_norms[i - 1](x))
             x = stage(x)
         return self.fc(self.head_norm(x.mean(dim=(2, 3))))
+
+
+def convnext_tiny(num_classes: int = 1000) -> ConvNeXt:
+    return ConvNeXt((3, 3, 9, 3), (96, 192, 384, 768), num_classes)
+
+
+def convnext_small(num_classes: int = 1000) -> ConvNeXt:
+    return ConvNeXt((3, 3, 27, 3), (96, 192, 384, 768), num_classes)

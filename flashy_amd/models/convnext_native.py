@@ -1,6 +1,7 @@
 # Copyright (c) Flashy-AMD authors.
 """ConvNeXt block on the native NHWC kernels (flashy_amd.nn): depthwise 7x7
-(csrc/conv_depthwise.hip), the dense MFMA path for the two 1x1 convs, and the
+(csrc/conv_depthwise.hip), the dense MFMA path for the two 1x1 convs (the
+pointwise kernels of csrc/conv_point.hip at widths off the 64 grid), and the
 row kernels of csrc/layernorm.hip for everything between the GEMMs.  Forward
 is five launches around the two GEMMs' own: depthwise conv, LayerNorm (which
 folds the conv's bias in), bias + GELU, layer scale + bias + residual.
@@ -21,16 +22,22 @@ from .convnext import ConvNeXt, ConvNeXtBlock
 
 
 class NativeConvNeXtBlock(nn.Module):
-    """NHWC bf16 in and out.  ``dim % 64 == 0``: the dense 1x1 path needs
-    K % 64 forward and C % 64 in backward-data."""
+    """NHWC bf16 in and out.  By default ``dim % 64 == 0`` and the 1x1 convs
+    ride the dense 8-wave kernels; ``dense_only=False`` admits every
+    ``dim % 8 == 0`` up to LayerNorm's 1024 and routes the widths off the 64
+    grid to the pointwise kernels (:class:`flashy_amd.nn.Conv2d`)."""
 
     def __init__(self, dim: int, kernel_size: int = 7,
-                 layer_scale_init: float = 1e-6):
+                 layer_scale_init: float = 1e-6, dense_only: bool = True):
         super().__init__()
-        if dim < 64 or dim % 64:
+        if dense_only and (dim < 64 or dim % 64):
             raise ValueError(
                 f"NativeConvNeXtBlock needs dim % 64 == 0 (the dense 1x1 conv "
-                f"kernels), got {dim}")
+                f"kernels; dense_only=False admits dim % 8 == 0), got {dim}")
+        if dim < 8 or dim % 8 or dim > 1024:
+            raise ValueError(
+                f"NativeConvNeXtBlock needs dim % 8 == 0 and 8 <= dim <= 1024, "
+                f"got {dim}")
         k = kernel_size
         self.dwconv = fnn.Conv2d(dim, dim, k, 1, k // 2, groups=dim)
         self.dwconv_bias = nn.Parameter(torch.zeros(dim))
@@ -51,7 +58,7 @@ class NativeConvNeXtBlock(nn.Module):
     @torch.no_grad()
     def from_torch(cls, twin: ConvNeXtBlock) -> "NativeConvNeXtBlock":
         dim = twin.gamma.numel()
-        block = cls(dim, twin.dwconv.kernel_size[0])
+        block = cls(dim, twin.dwconv.kernel_size[0], dense_only=dim % 64 == 0)
         block.dwconv.weight.copy_(twin.dwconv.weight.permute(0, 2, 3, 1))
         block.dwconv_bias.copy_(twin.dwconv.bias)
         block.norm.weight.copy_(twin.norm.weight)
@@ -70,16 +77,24 @@ class NativeConvNeXt(nn.Module):
     into the LayerNorm behind it.  Downsample: LayerNorm, the dense 2x2
     stride-2 conv, :func:`flashy_amd.nn.bias_add`.  Head: the pooling
     kernels, LayerNorm on ``[N, 1, 1, C]``, :class:`flashy_amd.nn.Linear`.
-    Every ``dims[i] % 64 == 0``, as the block demands."""
+    Every ``dims[i] % 64 == 0`` by default; ``dense_only=False`` admits
+    ``dims[i] % 8 == 0`` up to 1024 (ConvNeXt-T / -S: 96, 192, 384, 768), as
+    the block does, with ``dims[0]`` within the patch stem's rule."""
 
     def __init__(self, depths: tp.Sequence[int], dims: tp.Sequence[int],
-                 num_classes: int, patch: int = 4, in_chans: int = 3):
+                 num_classes: int, patch: int = 4, in_chans: int = 3,
+                 dense_only: bool = True):
         super().__init__()
         if len(depths) != 4 or len(dims) != 4 or \
-                any(d < 64 or d % 64 for d in dims):
+                (dense_only and any(d < 64 or d % 64 for d in dims)):
             raise ValueError(
                 f"NativeConvNeXt needs four stages with dims % 64 == 0 (the "
-                f"dense conv kernels), got depths={depths} dims={dims}")
+                f"dense conv kernels; dense_only=False admits dims % 8 == 0), "
+                f"got depths={depths} dims={dims}")
+        if any(d < 8 or d % 8 or d > 1024 for d in dims):
+            raise ValueError(
+                f"NativeConvNeXt needs dims % 8 == 0 and 8 <= dims <= 1024, "
+                f"got dims={dims}")
         self.stem = fnn.Conv2d(in_chans, dims[0], patch, patch, 0,
                                input_grad=False)
         if not self.stem.patch:
@@ -89,7 +104,8 @@ class NativeConvNeXt(nn.Module):
         self.stem_bias = nn.Parameter(torch.zeros(dims[0]))
         self.stem_norm = fnn.LayerNorm2d(dims[0], eps=1e-6)
         self.stages = nn.ModuleList(
-            nn.Sequential(*[NativeConvNeXtBlock(d) for _ in range(n)])
+            nn.Sequential(*[NativeConvNeXtBlock(d, dense_only=dense_only)
+                            for _ in range(n)])
             for n, d in zip(depths, dims))
         self.down_norms = nn.ModuleList(
             fnn.LayerNorm2d(d, eps=1e-6) for d in dims[:3])
@@ -119,7 +135,8 @@ class NativeConvNeXt(nn.Module):
         dims = [s[0].gamma.numel() if len(s) else c.out_channels
                 for s, c in zip(twin.stages, [twin.stem, *twin.down_convs])]
         net = cls(depths, dims, twin.fc.out_features,
-                  twin.stem.kernel_size[0], twin.stem.in_channels)
+                  twin.stem.kernel_size[0], twin.stem.in_channels,
+                  dense_only=all(d % 64 == 0 for d in dims))
         net.stem.weight.copy_(twin.stem.weight.permute(0, 2, 3, 1))
         net.stem_bias.copy_(twin.stem.bias)
         for mine, theirs in [(net.stem_norm, twin.stem_norm),
@@ -136,3 +153,13 @@ class NativeConvNeXt(nn.Module):
             nn.Sequential(*[NativeConvNeXtBlock.from_torch(b) for b in s])
             for s in twin.stages)
         return net
+
+
+def native_convnext_tiny(num_classes: int = 10) -> NativeConvNeXt:
+    return NativeConvNeXt((3, 3, 9, 3), (96, 192, 384, 768), num_classes,
+                          dense_only=False)
+
+
+def native_convnext_small(num_classes: int = 10) -> NativeConvNeXt:
+    return NativeConvNeXt((3, 3, 27, 3), (96, 192, 384, 768), num_classes,
+                          dense_only=False)

@@ -208,10 +208,50 @@ class _PatchConvFn(torch.autograd.Function):
                 None, None)
 
 
+class _PointwiseConvFn(torch.autograd.Function):
+    """Dense conv with kernel == stride in {1, 2}, pad 0 and a width off the
+    64 grid (csrc/conv_point.hip), weight [K, p, p, C]; backward-data reads
+    the same KRSC weight.  Emits no BatchNorm partials, as the grouped path."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, w: torch.Tensor, stride: int,
+                input_grad: bool):
+        w16 = _weight_bf16(w).contiguous()
+        x = x.contiguous()
+        d = ops.ConvDims.infer(x, w16, stride, 0)
+        y = x.new_empty((d.N, d.Ho, d.Wo, d.K))
+        ops.pwconv_fwd(x, w16, y, d)
+        ctx.save_for_backward(x, w16)
+        ctx.dims = d
+        ctx.input_grad = input_grad
+        ctx.w_ref = w
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        x, w16 = ctx.saved_tensors
+        d: ops.ConvDims = ctx.dims
+        dy = dy.contiguous()
+        dw_buf = None
+        direct = True
+        if ctx.needs_input_grad[1]:  # skip wgrad entirely for frozen weights
+            dw_buf, direct = _grad_target(ctx.w_ref)
+            ops.pwconv_wgrad(x, dy, dw_buf, d)
+        dx = None
+        if ctx.input_grad:
+            dx = x.new_empty(x.shape)
+            ops.pwconv_dgrad(dy, w16, dx, d)
+        return (dx, dw_buf if dw_buf is not None and not direct else None,
+                None, None)
+
+
 class Conv2d(nn.Module):
     """NHWC bf16 conv (no bias, as in ResNet).  Weight: [K, R, S, C] fp32;
     a patch conv (kernel == stride, no padding, 3 or 4 input channels:
-    :func:`flashy_amd.ops.patchconv_supported`) runs the patch kernels;
+    :func:`flashy_amd.ops.patchconv_supported`) runs the patch kernels; a
+    dense conv with kernel == stride in {1, 2}, no padding and a width off
+    the 64 grid (:func:`flashy_amd.ops.pwconv_supported`) runs the pointwise
+    kernels and sets ``pointwise``;
     with ``groups > 1`` a grouped 3x3 conv with weight [K, 3, 3, C // groups]
     (the shapes :func:`flashy_amd.ops.gconv_supported` accepts), or, with
     ``groups == in_channels == out_channels``, a depthwise k x k conv with
@@ -241,6 +281,10 @@ class Conv2d(nn.Module):
         # the cheap part of the rule first: most convs never ask the plan
         self.patch = groups == 1 and k == stride and padding == 0 \
             and in_channels <= 4 and ops.patchconv_supported(probe)
+        self.pointwise = groups == 1 and not self.patch and k == stride \
+            and k in (1, 2) and padding == 0 \
+            and (in_channels % 64 != 0 or out_channels % 64 != 0) \
+            and ops.pwconv_supported(probe)
         if groups != 1:
             if self.depthwise:
                 if not ops.dwconv_supported(probe):
@@ -271,6 +315,9 @@ class Conv2d(nn.Module):
         if self.patch:
             return _PatchConvFn.apply(x, self.weight, self.stride,
                                       self.input_grad and x.requires_grad)
+        if self.pointwise:
+            return _PointwiseConvFn.apply(x, self.weight, self.stride,
+                                          self.input_grad and x.requires_grad)
         return _ConvFn.apply(x, self.weight, self.stride, self.padding,
                              self.input_grad and x.requires_grad,
                              self._wt_view, self.feeds_bn and self.training)
@@ -290,6 +337,7 @@ class WtCache:
         convs = [m for m in model.modules()
                  if isinstance(m, Conv2d) and m.input_grad
                  and m.groups == 1   # grouped convs build their own operand
+                 and not m.pointwise  # reads the KRSC weight as it is
                  and m.weight.shape[-1] % 64 == 0]
         metas, total = [], 0
         mirrors = [getattr(c.weight, "_bf16_mirror", None) for c in convs]

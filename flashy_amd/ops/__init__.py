@@ -1109,6 +1109,87 @@ def patchconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# pointwise convolution (csrc/conv_point.hip): dense, kernel == stride in
+# {1, 2}, no padding, widths on the 8 grid.  Weights are [K, p, p, C] and are
+# read as they are by all three directions.
+# ---------------------------------------------------------------------------
+
+PWCONV_RULE = ("pointwise conv needs groups == 1, a square kernel equal to "
+               "the stride, 1 or 2, padding 0, in_channels % 8 == 0, "
+               "out_channels % 8 == 0, 8 <= out_channels <= 4096 and "
+               "8 <= kernel * kernel * in_channels <= 4096")
+
+
+def pwconv_plan(d: ConvDims) -> tp.Dict[str, int]:
+    """The plan of conv_point.hip for ``d`` (dims only): whether it serves
+    the shape, the column panels and reduction chunks of the forward and the
+    backward-data GEMM, and the weight gradient's fp32 slices."""
+    keys = ("ok", "fwd_panels", "fwd_chunks", "dgrad_panels", "dgrad_chunks",
+            "wgrad_splits")
+    return dict(zip(keys, require().pwconv_plan(*d)))
+
+
+def pwconv_supported(d: ConvDims) -> bool:
+    """Whether the pointwise kernels serve ``d`` (dims only; the plan lives
+    in conv_point.hip)."""
+    return require().pwconv_plan(*d)[0] > 0
+
+
+def _pwconv_check(d: ConvDims, w: torch.Tensor, w_dtype,
+                  acts: tp.Sequence[tp.Tuple[torch.Tensor,
+                                             tp.Tuple[int, ...]]]) -> int:
+    plan = require().pwconv_plan(*d)
+    if not plan[0]:
+        raise ValueError(
+            f"{PWCONV_RULE}, N >= 1, H, W >= kernel and Ho, Wo = "
+            f"H // kernel, W // kernel; got {d}")
+    tensors = [(w, w_dtype, (d.K, d.R, d.S, d.C))] + \
+        [(t, torch.bfloat16, shape) for t, shape in acts]
+    for t, dtype, shape in tensors:
+        if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() \
+                or tuple(t.shape) != shape or t.data_ptr() % 16:
+            raise ValueError(
+                f"{PWCONV_RULE}; tensors are contiguous, 16-byte aligned, on "
+                f"the device: wanted {dtype} {shape}, got {t.dtype} "
+                f"{tuple(t.shape)} strides {t.stride()} for {d}")
+    return plan[5]
+
+
+def pwconv_fwd(x: torch.Tensor, w16: torch.Tensor, y: torch.Tensor,
+               d: ConvDims) -> None:
+    """y[N, H // p, W // p, K] = pointwise conv of x[N, H, W, C] with the
+    bf16 weights ``w16`` [K, p, p, C]."""
+    _pwconv_check(d, w16, torch.bfloat16, [(x, (d.N, d.H, d.W, d.C)),
+                                           (y, (d.N, d.Ho, d.Wo, d.K))])
+    require().pwconv_fwd(x.data_ptr(), w16.data_ptr(), y.data_ptr(), *d,
+                         _stream())
+
+
+def pwconv_dgrad(dy: torch.Tensor, w16: torch.Tensor, dx: torch.Tensor,
+                 d: ConvDims) -> None:
+    """dx[N, H, W, C] from dy[N, Ho, Wo, K] and the same KRSC weights; every
+    element of dx is written once, the rows and columns no patch covers with
+    zeros."""
+    _pwconv_check(d, w16, torch.bfloat16, [(dy, (d.N, d.Ho, d.Wo, d.K)),
+                                           (dx, (d.N, d.H, d.W, d.C))])
+    require().pwconv_dgrad(dy.data_ptr(), w16.data_ptr(), dx.data_ptr(), *d,
+                           _stream())
+
+
+def pwconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor,
+                 d: ConvDims) -> None:
+    """Accumulates (+=) the fp32 weight gradient [K, p, p, C] into ``dw``.
+    The m-splits write fp32 slices that a combine kernel sums in split
+    order: no atomics, bitwise repeatable."""
+    splits = _pwconv_check(d, dw, torch.float32,
+                           [(x, (d.N, d.H, d.W, d.C)),
+                            (dy, (d.N, d.Ho, d.Wo, d.K))])
+    ws = torch.empty(splits, dw.numel(), dtype=torch.float32, device=x.device)
+    require().pwconv_wgrad(x.data_ptr(), dy.data_ptr(), ws.data_ptr(),
+                           dw.data_ptr(), *d, _stream())
+
+
+# ---------------------------------------------------------------------------
 # channel LayerNorm, bias+GELU, layer scale + residual (csrc/layernorm.hip).
 # Activations are contiguous bf16 [..., C] (NHWC: M = the product of the
 # leading dims); parameters and their gradients are fp32 [C].  Gradient

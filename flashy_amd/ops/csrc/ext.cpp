@@ -81,6 +81,14 @@ int launch_patchconv_dgrad(const void* dy, const void* w16, void* dx,
                            ConvDims d, hipStream_t stream);
 int launch_patchconv_wgrad(const void* x, const void* dy, void* ws, void* dw,
                            ConvDims d, hipStream_t stream);
+int pwconv_plan(ConvDims d, int* fwd_panels, int* fwd_chunks,
+                int* dgrad_panels, int* dgrad_chunks, int* wgrad_splits);
+int launch_pwconv_fwd(const void* x, const void* w16, void* y, ConvDims d,
+                      hipStream_t stream);
+int launch_pwconv_dgrad(const void* dy, const void* w16, void* dx, ConvDims d,
+                        hipStream_t stream);
+int launch_pwconv_wgrad(const void* x, const void* dy, void* ws, void* dw,
+                        ConvDims d, hipStream_t stream);
 int launch_bias_add(void* z, const void* b, int M, int C, hipStream_t stream);
 int launch_bias_add_bwd(const void* dout, void* ws, void* db, int M, int C,
                         hipStream_t stream);
@@ -570,6 +578,51 @@ PYBIND11_MODULE(_hip_ops, m) {
                       as_stream(stream)))
                   throw std::invalid_argument(
                       "patchconv_wgrad: unsupported shape");
+              check_last();
+          });
+    // pointwise conv (csrc/conv_point.hip): the plan's (served, forward
+    // panels, forward chunks, dgrad panels, dgrad chunks, wgrad splits); the
+    // launchers read the bf16 weights [K][p][p][C] as they are
+    m.def("pwconv_plan",
+          [](int N, int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad) {
+              int fp = 0, fc = 0, bp = 0, bc = 0, splits = 0;
+              const int ok = pwconv_plan(
+                  make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad), &fp,
+                  &fc, &bp, &bc, &splits);
+              return py::make_tuple(ok, fp, fc, bp, bc, splits);
+          });
+    m.def("pwconv_fwd",
+          [](uintptr_t x, uintptr_t w16, uintptr_t y, int N, int H, int W,
+             int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
+             uintptr_t stream) {
+              if (!launch_pwconv_fwd(
+                      (const void*)x, (const void*)w16, (void*)y,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      as_stream(stream)))
+                  throw std::invalid_argument("pwconv_fwd: unsupported shape");
+              check_last();
+          });
+    m.def("pwconv_dgrad",
+          [](uintptr_t dy, uintptr_t w16, uintptr_t dx, int N, int H, int W,
+             int C, int K, int R, int S, int Ho, int Wo, int stride, int pad,
+             uintptr_t stream) {
+              if (!launch_pwconv_dgrad(
+                      (const void*)dy, (const void*)w16, (void*)dx,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      as_stream(stream)))
+                  throw std::invalid_argument("pwconv_dgrad: unsupported shape");
+              check_last();
+          });
+    m.def("pwconv_wgrad",
+          [](uintptr_t x, uintptr_t dy, uintptr_t ws, uintptr_t dw, int N,
+             int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad, uintptr_t stream) {
+              if (!launch_pwconv_wgrad(
+                      (const void*)x, (const void*)dy, (void*)ws, (void*)dw,
+                      make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                      as_stream(stream)))
+                  throw std::invalid_argument("pwconv_wgrad: unsupported shape");
               check_last();
           });
     m.def("bias_add",
