@@ -19,6 +19,28 @@ from torch import nn
 from .. import nn as fnn
 
 
+BlockInput = tp.Union[torch.Tensor, tp.Tuple[torch.Tensor, torch.Tensor]]
+
+
+def _two_readers(x: BlockInput) -> tp.Tuple[torch.Tensor, torch.Tensor, bool]:
+    """A block reads its input twice, in conv1 and in the shortcut.  Fed the
+    pair of ``BatchNorm2d(split=True)`` each reader takes its own copy, so
+    the producing BatchNorm's backward receives the two gradients un-summed
+    (third value True: conv1 is its copy's only reader); fed a plain tensor
+    both read it and autograd adds the gradients."""
+    if isinstance(x, tuple):
+        return x[0], x[1], x[0] is not x[1]
+    return x, x, False
+
+
+def chain_blocks(blocks: tp.Sequence[nn.Module]) -> None:
+    """Residual blocks that feed one another, in order: every block but the
+    last hands its output on as a BatchNorm pair (``split_out``).  Only for
+    blocks whose outputs nothing else reads."""
+    for i, b in enumerate(blocks):
+        b.split_out = i + 1 < len(blocks)
+
+
 class NativeBasicBlock(nn.Module):
     expansion = 1
 
@@ -34,15 +56,19 @@ class NativeBasicBlock(nn.Module):
             self.dbn = fnn.BatchNorm2d(planes)
         else:
             self.dconv = None
+        # bn1's output has one reader, conv2 (see fnn.Conv2d.dgrad_to_bn)
+        self.conv2.dgrad_to_bn = True
+        self.split_out = False      # chain_blocks
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: BlockInput) -> BlockInput:
+        x, xs, own = _two_readers(x)
         if self.dconv is not None:
-            identity = self.dbn(self.dconv(x))
+            identity = self.dbn(self.dconv(xs))
         else:
-            identity = x
-        out = self.bn1(self.conv1(x), relu=True)
+            identity = xs
+        out = self.bn1(self.conv1(x, sole_reader=own), relu=True)
         out = self.conv2(out)
-        return self.bn2(out, res=identity, relu=True)
+        return self.bn2(out, res=identity, relu=True, split=self.split_out)
 
 
 class NativeBottleneck(nn.Module):
@@ -66,16 +92,21 @@ class NativeBottleneck(nn.Module):
             self.dbn = fnn.BatchNorm2d(planes * 4)
         else:
             self.dconv = None
+        # bn1's and bn2's outputs have one reader each
+        self.conv2.dgrad_to_bn = True
+        self.conv3.dgrad_to_bn = True
+        self.split_out = False      # chain_blocks
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: BlockInput) -> BlockInput:
+        x, xs, own = _two_readers(x)
         if self.dconv is not None:
-            identity = self.dbn(self.dconv(x))
+            identity = self.dbn(self.dconv(xs))
         else:
-            identity = x
-        out = self.bn1(self.conv1(x), relu=True)
+            identity = xs
+        out = self.bn1(self.conv1(x, sole_reader=own), relu=True)
         out = self.bn2(self.conv2(out), relu=True)
         out = self.conv3(out)
-        return self.bn3(out, res=identity, relu=True)
+        return self.bn3(out, res=identity, relu=True, split=self.split_out)
 
 
 class NativeResNet(nn.Module):
@@ -104,6 +135,8 @@ class NativeResNet(nn.Module):
         self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
         self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
         self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
+        chain_blocks([b for layer in (self.layer1, self.layer2, self.layer3,
+                                      self.layer4) for b in layer])
         self.fc = fnn.Linear(512 * block.expansion, num_classes)
         self._wt_cache = None
 
@@ -131,9 +164,12 @@ class NativeResNet(nn.Module):
             x = x.permute(0, 2, 3, 1).contiguous()
         if x.dtype != torch.bfloat16:
             x = x.to(torch.bfloat16)
-        x = self.stem_bn(self.stem_conv(x), relu=True)
+        # the CIFAR stem's BatchNorm feeds layer1 directly; behind the
+        # ImageNet stem's maxpool autograd keeps its own add
         if self.stem_pool is not None:
-            x = self.stem_pool(x)
+            x = self.stem_pool(self.stem_bn(self.stem_conv(x), relu=True))
+        else:
+            x = self.stem_bn(self.stem_conv(x), relu=True, split=True)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         # global average pool (NHWC) + fc as one fused head
         return fnn.pool_linear(x, self.fc.weight, self.fc.bias)

@@ -45,11 +45,69 @@ def _grad_target(p: torch.Tensor) -> tp.Tuple[torch.Tensor, bool]:
     return torch.zeros_like(p, memory_format=torch.contiguous_format), False
 
 
+# FLASHY_BN_GRAD_SOURCES=0 (read once, at import) restores the unfused
+# backward chain in the same build: autograd's add kernel for an activation
+# two layers read, and a split-K dgrad's own combine kernel (A/B traces; the
+# tests flip the variable itself).
+_FUSE_GRAD_SOURCES = os.environ.get("FLASHY_BN_GRAD_SOURCES", "1") != "0"
+# The single-kernel backward walks all M rows of its 8 channels on one CU, so
+# fp32 slices cost it M * zn rows of 32 bytes: at (M, C) = (1024, 512), zn = 5
+# it took 14.9 us against 7.3 + 4.4 us for the plain form plus the combine
+# kernel (profiles/README.md, r07a).  The added time is taken as linear in
+# M * zn (7.6 us at 5120); it stays under 3 us, below a combine launch, up to
+# 2048 rows.  Larger workspaces keep their combine kernel.
+_SMALL_FORM_WS_ROWS = 2048
+
+
+class _GradLink:
+    """Side channel from the one conv that reads a BatchNorm's output to that
+    BatchNorm's backward, for a split-K dgrad that leaves its fp32 slices
+    un-combined (``ops.conv_dgrad(defer_combine=True)``).  The conv claims
+    the link in forward and posts ``(dx, ws, zn)`` in backward; ``dx`` is the
+    unwritten tensor it returns to autograd.  The BatchNorm backward takes
+    the post and reads the slices, but only if that very tensor object
+    arrives, unmodified, as one of its gradients: if autograd summed it with
+    another gradient (in place or not), or a hook replaced it, its content
+    is lost and the backward raises instead of computing from it.  The link
+    keeps ``dx`` and ``ws`` alive until they are taken.
+
+    What stays unprotected is a reader of the conv's input gradient other
+    than the BatchNorm backward (a tensor hook or ``retain_grad`` on the
+    BatchNorm output, ``torch.autograd.grad`` with respect to it): it sees
+    unwritten memory.  ``Conv2d.dgrad_to_bn`` / ``sole_reader`` are set by a
+    model for whose tensors that cannot happen, never by default."""
+    __slots__ = ("claimed", "post", "max_ws_rows")
+
+    def __init__(self, max_ws_rows: tp.Optional[int] = None):
+        self.claimed = False
+        self.post = None
+        # the reader takes slices only while M * zn stays within this
+        self.max_ws_rows = max_ws_rows
+
+    def take(self, grads: tp.Sequence[tp.Optional[torch.Tensor]]
+             ) -> tp.Optional[tp.Tuple[int, torch.Tensor, int]]:
+        """(index of the deferred gradient in ``grads``, ws, zn) or None."""
+        post, self.post = self.post, None
+        if post is None:
+            return None
+        dx, version, ws, zn = post
+        for i, g in enumerate(grads):
+            if g is dx and g._version == version:
+                return i, ws, zn
+        raise RuntimeError(
+            "a split-K dgrad deferred its combine to this BatchNorm's "
+            "backward, but its gradient did not arrive as it was returned "
+            "(summed with another gradient, or replaced by a hook): clear "
+            "Conv2d.dgrad_to_bn / sole_reader for the conv that reads this "
+            "BatchNorm")
+
+
 class _ConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, w: torch.Tensor, stride: int, pad: int,
                 input_grad: bool, wt_cached: tp.Optional[torch.Tensor],
-                want_stats: bool = False):
+                want_stats: bool = False,
+                link: tp.Optional[_GradLink] = None):
         w16 = _weight_bf16(w)
         d = ops.ConvDims.infer(x, w16, stride, pad)
         y = x.new_empty((d.N, d.Ho, d.Wo, d.K))
@@ -62,6 +120,7 @@ class _ConvFn(torch.autograd.Function):
         ctx.input_grad = input_grad
         ctx.w_ref = w
         ctx.wt_cached = wt_cached
+        ctx.link = link
         return y
 
     @staticmethod
@@ -82,11 +141,18 @@ class _ConvFn(torch.autograd.Function):
                 if wt is None:
                     wt = w16.new_empty((d.R, d.S, d.C, d.K))
                     ops.weight_transpose(w16, wt)
-                ops.conv_dgrad(dy, wt, dx, d)
+                link = ctx.link
+                deferred = ops.conv_dgrad(
+                    dy, wt, dx, d, defer_combine=link is not None,
+                    defer_max_rows=link.max_ws_rows if link else None)
+                if deferred is not None:
+                    # dx stays unwritten: the BatchNorm backward that
+                    # produced x sums the slices itself (_GradLink)
+                    link.post = (dx, dx._version, *deferred)
             else:  # small-C edge conv (e.g. a discriminator RGB stem)
                 ops.conv_stem_dgrad(dy, w16, dx, d)
         return (dx, dw_buf if dw_buf is not None and not direct else None,
-                None, None, None, None, None)
+                None, None, None, None, None, None)
 
 
 def _gconv_dims(x_shape, K: int, stride: int, pad: int) -> ops.ConvDims:
@@ -269,6 +335,11 @@ class Conv2d(nn.Module):
         # when the conv output goes straight into a training BatchNorm2d,
         # the conv epilogue emits the BN sum/sumsq partials for free
         self.feeds_bn = feeds_bn
+        # set by a model (or said per call, forward's ``sole_reader``) when
+        # a BatchNorm output reaches this conv directly and nobody else reads
+        # that tensor or its gradient: a split-K dgrad then leaves its
+        # combine to that BatchNorm's backward (_GradLink)
+        self.dgrad_to_bn = False
         self._wt_view: tp.Optional[torch.Tensor] = None
         k = kernel_size
         self.depthwise = groups != 1 and groups == in_channels == out_channels
@@ -303,7 +374,9 @@ class Conv2d(nn.Module):
         fan_out = out_channels * k * k
         nn.init.normal_(self.weight, std=math.sqrt(2.0 / fan_out))
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor,
+                sole_reader: tp.Optional[bool] = None) -> torch.Tensor:
+        """``sole_reader`` overrides ``dgrad_to_bn`` for this call."""
         if self.depthwise:
             return _DepthwiseConvFn.apply(x, self.weight, self.stride,
                                           self.padding,
@@ -318,9 +391,20 @@ class Conv2d(nn.Module):
         if self.pointwise:
             return _PointwiseConvFn.apply(x, self.weight, self.stride,
                                           self.input_grad and x.requires_grad)
+        input_grad = self.input_grad and x.requires_grad
+        link = None
+        if sole_reader is None:
+            sole_reader = self.dgrad_to_bn
+        if sole_reader and _FUSE_GRAD_SOURCES and input_grad \
+                and torch.is_grad_enabled():
+            link = getattr(x, "_grad_link", None)
+            if link is not None and link.claimed:
+                link = None     # one deferred dgrad per BatchNorm
+            elif link is not None:
+                link.claimed = True
         return _ConvFn.apply(x, self.weight, self.stride, self.padding,
-                             self.input_grad and x.requires_grad,
-                             self._wt_view, self.feeds_bn and self.training)
+                             input_grad, self._wt_view,
+                             self.feeds_bn and self.training, link)
 
 
 class WtCache:
@@ -379,7 +463,7 @@ class _BnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
                 res: tp.Optional[torch.Tensor], relu: bool, slope: float,
-                module):
+                module, split: bool = False):
         N, H, W, C = x.shape
         M = N * H * W
         y = torch.empty_like(x)
@@ -422,15 +506,43 @@ class _BnFn(torch.autograd.Function):
         ctx.frozen_stats = not module.training
         ctx.has_res = res is not None
         ctx.refs = (gamma, beta)
-        return y
+        # backward takes its gradients as they come: None where an output
+        # went unused, never a zero-filled stand-in
+        ctx.set_materialize_grads(False)
+        ctx.split = split
+        ctx.link = None
+        if _FUSE_GRAD_SOURCES:
+            ctx.link = y._grad_link = _GradLink(
+                None if bwd_form == "chain" else _SMALL_FORM_WS_ROWS)
+        if not split:
+            return y
+        # the same storage on a second autograd edge: two readers of this
+        # activation (a conv and a shortcut) each return their gradient to
+        # an edge of their own, and backward forms the sum where it reads it
+        y2 = y.detach()
+        if ctx.link is not None:
+            y2._grad_link = ctx.link
+        return y, y2
 
     @staticmethod
-    def backward(ctx, dy: torch.Tensor):
+    def backward(ctx, *grads: tp.Optional[torch.Tensor]):
         x, y, work = ctx.saved_tensors
         gamma, beta = ctx.refs
         N, H, W, C = x.shape
         M = N * H * W
-        dy = dy.contiguous()
+        # dy = A [+ B]: A is a bf16 gradient or the fp32 slices a split-K
+        # dgrad left un-combined (zn > 0), B the second edge's gradient
+        taken = ctx.link.take(grads) if ctx.link is not None else None
+        zn = 0
+        if taken is not None:
+            i, dy, zn = taken
+            rest = [g for j, g in enumerate(grads) if j != i and g is not None]
+        else:
+            rest = [g for g in grads if g is not None]
+            if not rest:
+                return (None,) * 8
+            dy = rest.pop(0).contiguous()
+        dy_b = rest[0].contiguous() if rest else None
         # the sums are needed for dx, so the grads step always runs; frozen
         # gamma/beta just accumulate into a discarded temp instead of
         # param.grad (never pollute frozen params' grads).
@@ -442,18 +554,18 @@ class _BnFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         if ctx.bwd_form != "chain":
             # dz is the residual branch's gradient: written only if one reads it
-            dz = torch.empty_like(dy) if ctx.has_res else None
+            dz = torch.empty_like(x) if ctx.has_res else None
             ops.bn_bwd_small(dy, y, x, work, dz, dgamma, dbeta, dx, M, C,
                              ctx.relu, ctx.slope, write_dz=ctx.has_res,
-                             form=ctx.bwd_form)
+                             form=ctx.bwd_form, dy_b=dy_b, zn=zn)
         else:
             msplit = ops.bn_msplit(M, C)
             partials = torch.empty(msplit * 2 * C, dtype=torch.float32,
                                    device=x.device)
             bsums = torch.empty(2 * C, dtype=torch.float32, device=x.device)
-            dz = torch.empty_like(dy)
+            dz = torch.empty_like(x)
             ops.bn_bwd_reduce(dy, y, x, work, dz, partials, M, C, msplit,
-                              ctx.relu, ctx.slope)
+                              ctx.relu, ctx.slope, dy_b=dy_b, zn=zn)
             ops.bn_bwd_grads(partials, msplit, bsums, dgamma, dbeta, C)
             if ctx.frozen_stats:
                 # eval mode: the batch terms of dx vanish, dx = scale * dz.
@@ -466,7 +578,7 @@ class _BnFn(torch.autograd.Function):
                 dgamma if need_g and not g_direct else None,
                 dbeta if need_b and not b_direct else None,
                 dz if ctx.has_res else None,
-                None, None, None)
+                None, None, None, None)
 
 
 class _ConvTransposeFn(torch.autograd.Function):
@@ -778,9 +890,25 @@ class BatchNorm2d(nn.Module):
 
     def forward(self, x: torch.Tensor,
                 res: tp.Optional[torch.Tensor] = None,
-                relu: bool = False, slope: float = 0.0) -> torch.Tensor:
-        """``relu=True, slope=s`` applies LeakyReLU(s) (s=0: plain ReLU)."""
-        return _BnFn.apply(x, self.weight, self.bias, res, relu, slope, self)
+                relu: bool = False, slope: float = 0.0, split: bool = False
+                ) -> tp.Union[torch.Tensor, tp.Tuple[torch.Tensor, torch.Tensor]]:
+        """``relu=True, slope=s`` applies LeakyReLU(s) (s=0: plain ReLU).
+
+        ``split=True`` returns the output twice, ``(y, y2)``: one value, one
+        storage, two autograd edges.  A model that reads the output in two
+        places (a conv and a shortcut) gives each reader its own copy; the
+        two gradients then reach backward un-summed and the backward kernel
+        adds them as it reads them, instead of autograd launching an add.
+        The result is bitwise that of the summed gradient.  Treat the pair
+        as read-only."""
+        if not split:
+            return _BnFn.apply(x, self.weight, self.bias, res, relu, slope,
+                               self)
+        if not (_FUSE_GRAD_SOURCES and torch.is_grad_enabled()):
+            y = _BnFn.apply(x, self.weight, self.bias, res, relu, slope, self)
+            return y, y
+        return _BnFn.apply(x, self.weight, self.bias, res, relu, slope, self,
+                           True)
 
 
 def _param_grads(ctx, params: tp.Sequence[tp.Optional[torch.Tensor]],

@@ -781,7 +781,16 @@ def conv_stem_dgrad(dout: torch.Tensor, w_krsc: torch.Tensor,
 
 
 def conv_dgrad(dout: torch.Tensor, w_rsck: torch.Tensor, dx: torch.Tensor,
-               d: ConvDims) -> None:
+               d: ConvDims, defer_combine: bool = False,
+               defer_max_rows: tp.Optional[int] = None
+               ) -> tp.Optional[tp.Tuple[torch.Tensor, int]]:
+    """Backward-data conv into ``dx``.  With ``defer_combine`` a split-K
+    dgrad stops after its slices: ``dx`` is left unwritten and the fp32
+    workspace ``[zeff][M][C]`` comes back as ``(ws, zeff)`` for a reader that
+    sums the slices itself (:func:`bn_bwd_reduce` / :func:`bn_bwd_small` with
+    ``zn = zeff``, or :func:`splitk_combine`).  A single-pass dgrad, and a
+    workspace of more than ``defer_max_rows`` rows (``M * zeff``; None = any
+    size), writes ``dx`` and returns None either way."""
     ext = require()
     assert d.C % 64 == 0 and d.K % 32 == 0, d
     M = d.N * d.H * d.W
@@ -802,11 +811,27 @@ def conv_dgrad(dout: torch.Tensor, w_rsck: torch.Tensor, dx: torch.Tensor,
         ws = torch.empty(zeff * M * d.C, dtype=torch.float32, device=dout.device)
         ext.conv_dgrad_splitk(dout.data_ptr(), w_rsck.data_ptr(), ws.data_ptr(),
                               *d, spz, _stream())
-        ext.splitk_combine(ws.data_ptr(), dx.data_ptr(), M * d.C, zeff, False,
-                           _stream())
+        if defer_combine and (defer_max_rows is None
+                              or M * zeff <= defer_max_rows):
+            return ws, zeff
+        splitk_combine(ws, dx, zeff)
     else:
         ext.conv_dgrad(dout.data_ptr(), w_rsck.data_ptr(), dx.data_ptr(), *d,
                        _stream())
+    return None
+
+
+def splitk_combine(ws: torch.Tensor, out: torch.Tensor, zn: int,
+                   relu: bool = False) -> None:
+    """``out`` (bf16) = the ``zn`` fp32 slices of ``ws`` (each ``out.numel()``
+    long) summed in z order, optionally ReLU'd, rounded to bf16."""
+    total = out.numel()
+    assert ws.dtype == torch.float32 and out.dtype == torch.bfloat16
+    assert ws.is_contiguous() and out.is_contiguous()
+    assert zn >= 1 and ws.numel() >= zn * total and total % 4 == 0, \
+        (ws.numel(), zn, total)
+    require().splitk_combine(ws.data_ptr(), out.data_ptr(), total, zn, relu,
+                             _stream())
 
 
 DGRAD_S2_FORMS = {"generic": 0, "par8": 1, "par4": 2, "scat2": 3}
@@ -1389,13 +1414,42 @@ def bn_apply(x, res, y, work, M: int, C: int, relu: bool,
                        _stream())
 
 
+def _bn_dy_sources(name: str, dy, dy_b, zn: int, M: int, C: int) -> None:
+    """``dy = A [+ B]`` of the BatchNorm backward kernels: A is ``dy``, a
+    bf16 ``[M, C]`` tensor, or with ``zn >= 1`` the fp32 workspace of a
+    split-K dgrad (``zn`` slices of ``M*C``, summed in z order and rounded to
+    bf16 as :func:`splitk_combine` does); B is ``dy_b``, a bf16 ``[M, C]``
+    tensor added as ``torch.add`` on bf16 adds it.  The kernels read through
+    raw pointers, so every size is checked here."""
+    if zn:
+        if zn < 1 or dy.dtype != torch.float32 or dy.numel() < zn * M * C:
+            raise ValueError(f"{name}: a split-K source needs zn >= 1 fp32 "
+                             f"slices of M*C = {M * C}, got zn = {zn}, "
+                             f"{dy.dtype}, {dy.numel()} elements")
+    elif dy.dtype != torch.bfloat16 or dy.numel() != M * C:
+        raise ValueError(f"{name}: dy must be bf16 with M*C = {M * C} "
+                         f"elements, got {dy.dtype}, {dy.numel()}")
+    if dy_b is not None and (dy_b.dtype != torch.bfloat16
+                             or dy_b.numel() != M * C):
+        raise ValueError(f"{name}: dy_b must be bf16 with M*C = {M * C} "
+                         f"elements, got {dy_b.dtype}, {dy_b.numel()}")
+    for t in (dy, dy_b):
+        if t is not None and (not t.is_contiguous() or t.data_ptr() % 16):
+            raise ValueError(f"{name}: gradient sources must be contiguous "
+                             "and 16-byte aligned")
+
+
 def bn_bwd_reduce(dy, y, x, work, dz_out, partials, M: int, C: int,
-                  msplit: int, relu: bool, slope: float = 0.0) -> None:
+                  msplit: int, relu: bool, slope: float = 0.0,
+                  dy_b: tp.Optional[torch.Tensor] = None, zn: int = 0) -> None:
+    """Backward pass 1 over ``dy [+ dy_b]`` (:func:`_bn_dy_sources`)."""
     _bn_width("bn_bwd_reduce", C, 64)
+    _bn_dy_sources("bn_bwd_reduce", dy, dy_b, zn, M, C)
     require().bn_bwd_reduce(dy.data_ptr(), y.data_ptr(), x.data_ptr(),
                             work.data_ptr(), dz_out.data_ptr(),
                             partials.data_ptr(), M, C, msplit, relu, slope,
-                            _stream())
+                            _stream(),
+                            dy_b.data_ptr() if dy_b is not None else 0, zn)
 
 
 def bn_bwd_grads(partials, msplit: int, bsums, dgamma, dbeta, C: int) -> None:
@@ -1443,14 +1497,17 @@ def bn_fwd_small(partials, msplit: int, gamma, beta, rmean, rvar, work, x,
 
 def bn_bwd_small(dy, y, x, work, dz, dgamma, dbeta, dx, M: int, C: int,
                  relu: bool, slope: float = 0.0, write_dz: bool = True,
-                 form: str = "regs8") -> None:
+                 form: str = "regs8",
+                 dy_b: tp.Optional[torch.Tensor] = None, zn: int = 0) -> None:
     """:func:`bn_bwd_reduce` + :func:`bn_bwd_grads` + :func:`bn_bwd_apply` in
     one launch through the named form, whatever the plan says.  ``dgamma`` /
     ``dbeta`` are accumulated (+=); ``dz`` is written only with ``write_dz``
-    (and may be None without it).
+    (and may be None without it).  The gradient is ``dy [+ dy_b]``
+    (:func:`_bn_dy_sources`).
     Raises where the form cannot run the shape."""
     assert all(t.is_contiguous() for t in (dy, y, x, dx))
     assert x.numel() == M * C
+    _bn_dy_sources("bn_bwd_small", dy, dy_b, zn, M, C)
     assert dz.is_contiguous() if write_dz else True
     if form == "chain":
         raise ValueError("bn_bwd_small: 'chain' is not a single-kernel form")
@@ -1458,7 +1515,8 @@ def bn_bwd_small(dy, y, x, work, dz, dgamma, dbeta, dx, M: int, C: int,
         dy.data_ptr(), y.data_ptr(), x.data_ptr(), work.data_ptr(),
         dz.data_ptr() if dz is not None else 0, dgamma.data_ptr(),
         dbeta.data_ptr(), dx.data_ptr(),
-        M, C, relu, slope, write_dz, BN_BWD_SMALL_FORMS[form], _stream())
+        M, C, relu, slope, write_dz, BN_BWD_SMALL_FORMS[form], _stream(),
+        dy_b.data_ptr() if dy_b is not None else 0, zn)
 
 
 # ---------------------------------------------------------------------------

@@ -9,14 +9,23 @@ CPU-only build box too.
 """
 from __future__ import annotations
 
+import os
 import subprocess
 import sys
 import sysconfig
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 ARCH = "gfx950"
+# Translation units built without packed fp32 instructions (v_pk_add_f32,
+# v_pk_mul_f32, v_pk_fma_f32).  Each lane's arithmetic is the same IEEE
+# operation either way, so results do not move; these kernels are bound by
+# memory and launch latency, not by the VALU.  New kernel code goes here.
+SCALAR_FP32 = {"batchnorm.hip"}
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def so_path() -> Path:
@@ -46,17 +55,31 @@ def build(verbose: bool = True, force: bool = False) -> Path:
         return out
     import pybind11
     py_include = sysconfig.get_paths()["include"]
-    cmd = [
-        "hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17",
-        "-fPIC", "-shared",
+    base = [
+        "hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
         "-DNDEBUG",
         f"-I{py_include}", f"-I{pybind11.get_include()}", f"-I{CSRC}",
-        *[str(s) for s in sources()],
-        "-o", str(out),
     ]
-    if verbose:
-        print("[flashy_amd.ops.build]", " ".join(cmd))
-    subprocess.run(cmd, check=True)
+
+    def run(cmd: list) -> None:
+        if verbose:
+            print("[flashy_amd.ops.build]", " ".join(cmd))
+        subprocess.run(cmd, check=True)
+
+    # one object per source (flags differ per file), a few at a time, then
+    # one link; the objects live in a temporary folder, not in the tree
+    with tempfile.TemporaryDirectory(prefix="flashy_amd_build_") as tmp:
+        def compile_one(src: Path) -> str:
+            obj = str(Path(tmp) / (src.name + ".o"))
+            flags = NO_PACKED_FP32 if src.name in SCALAR_FP32 else []
+            run(base + flags + ["-c", str(src), "-o", obj])
+            return obj
+
+        jobs = max(1, min(8, os.cpu_count() or 1))
+        with ThreadPoolExecutor(jobs) as pool:
+            objs = list(pool.map(compile_one, sources()))
+        run(["hipcc", f"--offload-arch={ARCH}", "-fPIC", "-shared", *objs,
+             "-o", str(out)])
     return out
 
 

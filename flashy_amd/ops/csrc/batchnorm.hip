@@ -293,14 +293,73 @@ static inline int apply_mpb(int64_t M, int C) {
     return (int)((M + mblocks - 1) / mblocks);
 }
 
+template <int CW> struct bn_vec {
+    using type = __attribute__((ext_vector_type(CW))) short;
+};
+
+// ---------------------------------------------------------------------------
+// Gradient source of backward pass 1: dy = A [+ B], formed where it is read.
+// A is a bf16 [M, C] tensor (WS = false) or the fp32 workspace of a split-K
+// dgrad (WS = true: zn slices, `slice` = M*C floats apart); B (ADDB) is a
+// bf16 [M, C] tensor, the other gradient of an activation that two layers
+// read.  The arithmetic is that of the kernels this replaces, so dy is
+// bitwise what they would have stored: the slices are summed in z order and
+// rounded to bf16 as k_splitk_combine does, and A + B is one fp32 add of the
+// two bf16 values rounded to bf16, as the framework's bf16 add.  With
+// WS = ADDB = false this is the plain 16-byte load.
+// ---------------------------------------------------------------------------
+template <int CW, bool WS, bool ADDB>
+__device__ __forceinline__ typename bn_vec<CW>::type bn_dy_load(
+        const void* __restrict__ a, const uint16_t* __restrict__ b,
+        int64_t off, int zn, int64_t slice) {
+    using vec = typename bn_vec<CW>::type;
+    static_assert(CW % 4 == 0, "fp32 slices are read as float4");
+    vec g;
+    if (WS) {
+        const float* ws = (const float*)a + off;
+        float4 acc[CW / 4];
+#pragma unroll
+        for (int q = 0; q < CW / 4; ++q)
+            acc[q] = *reinterpret_cast<const float4*>(ws + 4 * q);
+        for (int z = 1; z < zn; ++z) {
+            const float* wz = ws + (int64_t)z * slice;
+#pragma unroll
+            for (int q = 0; q < CW / 4; ++q) {
+                const float4 v = *reinterpret_cast<const float4*>(wz + 4 * q);
+                acc[q].x += v.x; acc[q].y += v.y;
+                acc[q].z += v.z; acc[q].w += v.w;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < CW / 4; ++q) {
+            ((uint16_t*)&g)[4 * q + 0] = f32_to_bf16(acc[q].x);
+            ((uint16_t*)&g)[4 * q + 1] = f32_to_bf16(acc[q].y);
+            ((uint16_t*)&g)[4 * q + 2] = f32_to_bf16(acc[q].z);
+            ((uint16_t*)&g)[4 * q + 3] = f32_to_bf16(acc[q].w);
+        }
+    } else {
+        g = *reinterpret_cast<const vec*>((const uint16_t*)a + off);
+    }
+    if (ADDB) {
+        const vec bv = *reinterpret_cast<const vec*>(b + off);
+#pragma unroll
+        for (int j = 0; j < CW; ++j)
+            ((uint16_t*)&g)[j] = f32_to_bf16(
+                bf16_to_f32(((const uint16_t*)&g)[j]) +
+                bf16_to_f32(((const uint16_t*)&bv)[j]));
+    }
+    return g;
+}
+
 // ---------------------------------------------------------------------------
 // bwd 1: dz = dy * (y > 0) [if relu]; per-channel partial sums of dz and
-// dz*xhat.  Same geometry as stats.
+// dz*xhat.  Same geometry as stats.  dy = A [+ B] (bn_dy_load).
 // ---------------------------------------------------------------------------
 
-template <bool RELU>
+template <bool RELU, bool WS, bool ADDB>
 __global__ void __launch_bounds__(256)
-k_bn_bwd_reduce(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
+k_bn_bwd_reduce(const void* __restrict__ dy, const uint16_t* __restrict__ dyb,
+                int zn, const uint16_t* __restrict__ y,
                 const uint16_t* __restrict__ x, const float* __restrict__ work,
                 uint16_t* __restrict__ dz_out, float* __restrict__ partials,
                 int64_t M, int C, int msplit, int m_per_block, float slope) {
@@ -318,7 +377,7 @@ k_bn_bwd_reduce(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
     float s[8] = {}, sx[8] = {};
     for (int64_t m = m0 + mlane; m < m1; m += 32) {
         const int64_t off = m * C + cbase + c8;
-        const short8 g8 = *reinterpret_cast<const short8*>(dy + off);
+        const short8 g8 = bn_dy_load<8, WS, ADDB>(dy, dyb, off, zn, M * C);
         const short8 x8 = *reinterpret_cast<const short8*>(x + off);
         short8 y8 = {};
         if (RELU) y8 = *reinterpret_cast<const short8*>(y + off);
@@ -487,20 +546,17 @@ k_bn_fwd_small(const float* __restrict__ partials, int msplit,
     }
 }
 
-template <int CW> struct bn_vec {
-    using type = __attribute__((ext_vector_type(CW))) short;
-};
-
 // One row of backward pass 1: dz = bf16(dy * relu-mask), sums of the
 // unrounded g and g*xhat — the expressions of k_bn_bwd_reduce.
-template <bool RELU, int CW>
+template <bool RELU, int CW, bool WS, bool ADDB>
 __device__ __forceinline__ void bn_bwd_row(
-        const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
+        const void* __restrict__ dy, const uint16_t* __restrict__ dyb, int zn,
+        int64_t slice, const uint16_t* __restrict__ y,
         const uint16_t* __restrict__ x, int64_t off, const float* mean,
         const float* invstd, float slope, float* s, float* sx,
         typename bn_vec<CW>::type* dz_out, typename bn_vec<CW>::type* x_out) {
     using vec = typename bn_vec<CW>::type;
-    const vec gv = *reinterpret_cast<const vec*>(dy + off);
+    const vec gv = bn_dy_load<CW, WS, ADDB>(dy, dyb, off, zn, slice);
     const vec xv = *reinterpret_cast<const vec*>(x + off);
     vec yv = {};
     if (RELU) yv = *reinterpret_cast<const vec*>(y + off);
@@ -531,9 +587,11 @@ __device__ __forceinline__ void bn_bwd_row(
 // channel groups share each 128-byte line of a row: block b takes group
 // (b%8)*(grid/8) + b/8, so the blocks one XCD receives own adjacent groups
 // and its L2 fetches a line once (placement only; any order is correct).
-template <bool RELU, bool WRITE_DZ, int CW, int R>
+// dy = A [+ B] (bn_dy_load) is formed in pass 1 and lives on only as dz.
+template <bool RELU, bool WRITE_DZ, int CW, int R, bool WS, bool ADDB>
 __global__ void __launch_bounds__(256)
-k_bn_bwd_small(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
+k_bn_bwd_small(const void* __restrict__ dy, const uint16_t* __restrict__ dyb,
+               int zn, const uint16_t* __restrict__ y,
                const uint16_t* __restrict__ x, const float* __restrict__ work,
                uint16_t* __restrict__ dz_out, float* __restrict__ dgamma,
                float* __restrict__ dbeta, uint16_t* __restrict__ dx,
@@ -558,8 +616,9 @@ k_bn_bwd_small(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
         const int64_t m = t + 256 * r;
         if (m < M) {
             const int64_t off = m * C + c0;
-            bn_bwd_row<RELU, CW>(dy, y, x, off, mean, invstd, slope, s, sx,
-                                 &dzk[r], &xk[r]);
+            bn_bwd_row<RELU, CW, WS, ADDB>(dy, dyb, zn, M * C, y, x, off, mean,
+                                           invstd, slope, s, sx, &dzk[r],
+                                           &xk[r]);
             if (WRITE_DZ) *reinterpret_cast<vec*>(dz_out + off) = dzk[r];
         }
     }
@@ -680,23 +739,41 @@ extern "C" void launch_bn_apply(const void* x, const void* res, void* y,
             (const uint16_t*)x, nullptr, (uint16_t*)y, (const float*)work, M, C, slope);
 }
 
+// dy = A [+ B]: `a` is a bf16 [M, C] tensor (zn == 0) or a split-K fp32
+// workspace of zn >= 1 slices; `b` is a bf16 [M, C] tensor or null.
+extern "C" void launch_bn_bwd_reduce_src(const void* a, const void* b, int zn,
+                                         const void* y, const void* x,
+                                         const void* work, void* dz_out,
+                                         void* partials, int64_t M, int C,
+                                         int msplit, int relu, float slope,
+                                         hipStream_t stream) {
+    const int mpb = (int)((M + msplit - 1) / msplit);
+    dim3 grid((unsigned)(C / 64), (unsigned)msplit);
+#define BN_BWD_REDUCE(RELU, WS, ADDB)                                         \
+    k_bn_bwd_reduce<RELU, WS, ADDB><<<grid, 256, 0, stream>>>(                \
+        a, (const uint16_t*)b, zn, (const uint16_t*)y, (const uint16_t*)x,    \
+        (const float*)work, (uint16_t*)dz_out, (float*)partials, M, C,        \
+        msplit, mpb, slope)
+#define BN_BWD_REDUCE_SRC(RELU)                                               \
+    do {                                                                      \
+        if (zn && b) BN_BWD_REDUCE(RELU, true, true);                         \
+        else if (zn) BN_BWD_REDUCE(RELU, true, false);                        \
+        else if (b) BN_BWD_REDUCE(RELU, false, true);                         \
+        else BN_BWD_REDUCE(RELU, false, false);                               \
+    } while (0)
+    if (relu) BN_BWD_REDUCE_SRC(true);
+    else BN_BWD_REDUCE_SRC(false);
+#undef BN_BWD_REDUCE_SRC
+#undef BN_BWD_REDUCE
+}
+
 extern "C" void launch_bn_bwd_reduce(const void* dy, const void* y,
                                      const void* x, const void* work,
                                      void* dz_out, void* partials, int64_t M,
                                      int C, int msplit, int relu, float slope,
                                      hipStream_t stream) {
-    const int mpb = (int)((M + msplit - 1) / msplit);
-    dim3 grid((unsigned)(C / 64), (unsigned)msplit);
-    if (relu)
-        k_bn_bwd_reduce<true><<<grid, 256, 0, stream>>>(
-            (const uint16_t*)dy, (const uint16_t*)y, (const uint16_t*)x,
-            (const float*)work, (uint16_t*)dz_out, (float*)partials, M, C,
-            msplit, mpb, slope);
-    else
-        k_bn_bwd_reduce<false><<<grid, 256, 0, stream>>>(
-            (const uint16_t*)dy, (const uint16_t*)y, (const uint16_t*)x,
-            (const float*)work, (uint16_t*)dz_out, (float*)partials, M, C,
-            msplit, mpb, slope);
+    launch_bn_bwd_reduce_src(dy, nullptr, 0, y, x, work, dz_out, partials, M,
+                             C, msplit, relu, slope, stream);
 }
 
 extern "C" void launch_bn_bwd_grads(const void* partials, int msplit,
@@ -775,15 +852,16 @@ extern "C" int launch_bn_fwd_small(const void* partials, int msplit,
     return 1;
 }
 
-template <int CW, int R>
-static void bn_bwd_small_launch(const void* dy, const void* y, const void* x,
+template <int CW, int R, bool WS, bool ADDB>
+static void bn_bwd_small_launch(const void* a, const void* b, int zn,
+                                const void* y, const void* x,
                                 const void* work, void* dz, void* dgamma,
                                 void* dbeta, void* dx, int64_t M, int C,
                                 int relu, float slope, int write_dz,
                                 hipStream_t stream) {
 #define BN_BWD_SMALL(RELU, WDZ)                                               \
-    k_bn_bwd_small<RELU, WDZ, CW, R><<<C / CW, 256, 0, stream>>>(             \
-        (const uint16_t*)dy, (const uint16_t*)y, (const uint16_t*)x,          \
+    k_bn_bwd_small<RELU, WDZ, CW, R, WS, ADDB><<<C / CW, 256, 0, stream>>>(   \
+        a, (const uint16_t*)b, zn, (const uint16_t*)y, (const uint16_t*)x,    \
         (const float*)work, (uint16_t*)dz, (float*)dgamma, (float*)dbeta,     \
         (uint16_t*)dx, M, C, slope)
     if (relu && write_dz) BN_BWD_SMALL(true, true);
@@ -793,20 +871,42 @@ static void bn_bwd_small_launch(const void* dy, const void* y, const void* x,
 #undef BN_BWD_SMALL
 }
 
+// dy = A [+ B] as in launch_bn_bwd_reduce_src.
+extern "C" int launch_bn_bwd_small_src(const void* a, const void* b, int zn,
+                                       const void* y, const void* x,
+                                       const void* work, void* dz,
+                                       void* dgamma, void* dbeta, void* dx,
+                                       int64_t M, int C, int relu, float slope,
+                                       int write_dz, int form,
+                                       hipStream_t stream) {
+    if (form != 1 || M < 1 || C < 8 || C % 8) return 0;
+    const int rows = bn_bwd_small_rows(M);
+    if (!rows) return 0;
+#define BN_BWD_GO(R, WS, ADDB)                                                \
+    bn_bwd_small_launch<8, R, WS, ADDB>(a, b, zn, y, x, work, dz, dgamma,     \
+                                        dbeta, dx, M, C, relu, slope,         \
+                                        write_dz, stream)
+#define BN_BWD_GO_SRC(R)                                                      \
+    do {                                                                      \
+        if (zn && b) BN_BWD_GO(R, true, true);                                \
+        else if (zn) BN_BWD_GO(R, true, false);                               \
+        else if (b) BN_BWD_GO(R, false, true);                                \
+        else BN_BWD_GO(R, false, false);                                      \
+    } while (0)
+    if (rows == 4) BN_BWD_GO_SRC(4);
+    else BN_BWD_GO_SRC(16);
+#undef BN_BWD_GO_SRC
+#undef BN_BWD_GO
+    return 1;
+}
+
 extern "C" int launch_bn_bwd_small(const void* dy, const void* y,
                                    const void* x, const void* work, void* dz,
                                    void* dgamma, void* dbeta, void* dx,
                                    int64_t M, int C, int relu, float slope,
                                    int write_dz, int form,
                                    hipStream_t stream) {
-    if (form != 1 || M < 1 || C < 8 || C % 8) return 0;
-    const int rows = bn_bwd_small_rows(M);
-    if (!rows) return 0;
-#define BN_BWD_GO(CW, R)                                                      \
-    bn_bwd_small_launch<CW, R>(dy, y, x, work, dz, dgamma, dbeta, dx, M, C,   \
-                               relu, slope, write_dz, stream)
-    if (rows == 4) BN_BWD_GO(8, 4);
-    else BN_BWD_GO(8, 16);
-#undef BN_BWD_GO
-    return 1;
+    return launch_bn_bwd_small_src(dy, nullptr, 0, y, x, work, dz, dgamma,
+                                   dbeta, dx, M, C, relu, slope, write_dz,
+                                   form, stream);
 }

@@ -125,6 +125,11 @@ void launch_bn_bwd_reduce(const void* dy, const void* y, const void* x,
                           const void* work, void* dz_out, void* partials,
                           int64_t M, int C, int msplit, int relu, float slope,
                           hipStream_t stream);
+void launch_bn_bwd_reduce_src(const void* a, const void* b, int zn,
+                              const void* y, const void* x, const void* work,
+                              void* dz_out, void* partials, int64_t M, int C,
+                              int msplit, int relu, float slope,
+                              hipStream_t stream);
 void launch_bn_bwd_grads(const void* partials, int msplit, void* bsums,
                          void* dgamma, void* dbeta, int C, hipStream_t stream);
 void launch_bn_bwd_apply(const void* dz, const void* x, const void* work,
@@ -141,6 +146,11 @@ int launch_bn_bwd_small(const void* dy, const void* y, const void* x,
                         const void* work, void* dz, void* dgamma, void* dbeta,
                         void* dx, int64_t M, int C, int relu, float slope,
                         int write_dz, int form, hipStream_t stream);
+int launch_bn_bwd_small_src(const void* a, const void* b, int zn,
+                            const void* y, const void* x, const void* work,
+                            void* dz, void* dgamma, void* dbeta, void* dx,
+                            int64_t M, int C, int relu, float slope,
+                            int write_dz, int form, hipStream_t stream);
 void launch_fused_sgd(void* p, const void* g, void* m, void* p_bf16, int64_t n,
                       float lr, float momentum, float wd, float grad_scale,
                       int nesterov, const void* hyper, hipStream_t stream);
@@ -739,17 +749,27 @@ PYBIND11_MODULE(_hip_ops, m) {
                               as_stream(stream));
               check_last();
           });
+    // `dy_b`, `zn` (trailing, default 0): dy = A [+ B].  zn >= 1 makes `dy`
+    // the fp32 workspace of a split-K dgrad (zn slices of M*C), dy_b != 0
+    // adds a second bf16 [M, C] gradient; both sums are formed in the kernel.
     m.def("bn_bwd_reduce",
           [](uintptr_t dy, uintptr_t y, uintptr_t x, uintptr_t work,
              uintptr_t dz_out, uintptr_t partials, int64_t M, int C,
-             int msplit, bool relu, float slope, uintptr_t stream) {
-              launch_bn_bwd_reduce((const void*)dy, (const void*)y,
-                                   (const void*)x, (const void*)work,
-                                   (void*)dz_out, (void*)partials, M, C,
-                                   msplit, relu ? 1 : 0, slope,
-                                   as_stream(stream));
+             int msplit, bool relu, float slope, uintptr_t stream,
+             uintptr_t dy_b, int zn) {
+              if (zn < 0) throw std::invalid_argument("bn_bwd_reduce: zn < 0");
+              launch_bn_bwd_reduce_src((const void*)dy, (const void*)dy_b, zn,
+                                       (const void*)y, (const void*)x,
+                                       (const void*)work, (void*)dz_out,
+                                       (void*)partials, M, C, msplit,
+                                       relu ? 1 : 0, slope, as_stream(stream));
               check_last();
-          });
+          },
+          py::arg("dy"), py::arg("y"), py::arg("x"), py::arg("work"),
+          py::arg("dz_out"), py::arg("partials"), py::arg("M"), py::arg("C"),
+          py::arg("msplit"), py::arg("relu"), py::arg("slope"),
+          py::arg("stream"), py::arg("dy_b") = (uintptr_t)0,
+          py::arg("zn") = 0);
     m.def("bn_bwd_grads",
           [](uintptr_t partials, int msplit, uintptr_t bsums, uintptr_t dgamma,
              uintptr_t dbeta, int C, uintptr_t stream) {
@@ -793,16 +813,23 @@ PYBIND11_MODULE(_hip_ops, m) {
           [](uintptr_t dy, uintptr_t y, uintptr_t x, uintptr_t work,
              uintptr_t dz, uintptr_t dgamma, uintptr_t dbeta, uintptr_t dx,
              int64_t M, int C, bool relu, float slope, bool write_dz, int form,
-             uintptr_t stream) {
-              if (!launch_bn_bwd_small(
-                      (const void*)dy, (const void*)y, (const void*)x,
-                      (const void*)work, (void*)dz, (void*)dgamma,
-                      (void*)dbeta, (void*)dx, M, C, relu ? 1 : 0, slope,
-                      write_dz ? 1 : 0, form, as_stream(stream)))
+             uintptr_t stream, uintptr_t dy_b, int zn) {
+              if (zn < 0) throw std::invalid_argument("bn_bwd_small: zn < 0");
+              if (!launch_bn_bwd_small_src(
+                      (const void*)dy, (const void*)dy_b, zn, (const void*)y,
+                      (const void*)x, (const void*)work, (void*)dz,
+                      (void*)dgamma, (void*)dbeta, (void*)dx, M, C,
+                      relu ? 1 : 0, slope, write_dz ? 1 : 0, form,
+                      as_stream(stream)))
                   throw std::invalid_argument(
                       "bn_bwd_small: form cannot run this shape");
               check_last();
-          });
+          },
+          py::arg("dy"), py::arg("y"), py::arg("x"), py::arg("work"),
+          py::arg("dz"), py::arg("dgamma"), py::arg("dbeta"), py::arg("dx"),
+          py::arg("M"), py::arg("C"), py::arg("relu"), py::arg("slope"),
+          py::arg("write_dz"), py::arg("form"), py::arg("stream"),
+          py::arg("dy_b") = (uintptr_t)0, py::arg("zn") = 0);
 
     // `hyper` (trailing, default 0): device block written by optim_prepare;
     // when set, the kernel reads lr and the clip coefficient from it.

@@ -30,7 +30,7 @@ with torch.no_grad():
     a_t = twin.stem(x)
     d = (a_n.float().permute(0, 3, 1, 2) - a_t).abs().max().item()
     print("after stem:", d, a_t.abs().max().item())
-    b_n = model.layer1(a_n)
+    b_n, _ = model.layer1(a_n)   # handed on as a BatchNorm pair
     b_t = twin.layer1(a_t)
     d = (b_n.float().permute(0, 3, 1, 2) - b_t).abs().max().item()
     print("after layer1:", d, b_t.abs().max().item())
