@@ -1061,3 +1061,100 @@ def scale_residual(z: torch.Tensor, bias: torch.Tensor, scale: torch.Tensor,
     """``res + scale * (z + bias)`` over NHWC bf16 ``z`` / ``res`` with fp32
     per-channel ``bias`` and layer ``scale``, one launch."""
     return _ScaleResidualFn.apply(z, bias, scale, res)
+
+
+def _grn_coefs(x: torch.Tensor):
+    n, c = x.shape[0], x.shape[-1]
+    return (torch.empty(n, c, dtype=torch.float32, device=x.device),
+            torch.empty(n, c, dtype=torch.float32, device=x.device),
+            torch.empty(n, dtype=torch.float32, device=x.device))
+
+
+class _GrnFn(torch.autograd.Function):
+    """Global response normalization of an NHWC tensor (csrc/grn.hip); saves
+    the input, Nx, a = 1 + gamma * Nx and each image's 1 / (mu + eps), not
+    the output."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                eps: float):
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        nx, a, rden = _grn_coefs(x)
+        ops.grn_fwd(x, gamma, beta, out, nx, a, rden, eps)
+        ctx.save_for_backward(x, nx, a, rden)
+        ctx.refs = (gamma, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        x, nx, a, rden = ctx.saved_tensors
+        gamma, beta = ctx.refs
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        (dgamma, dbeta), grads = _param_grads(ctx, (gamma, beta), 1)
+        ops.grn_bwd(dout.contiguous(), x, nx, a, rden, gamma, dx, dgamma,
+                    dbeta)
+        return (dx, *grads, None)
+
+
+class GRN(nn.Module):
+    """Global response normalization (ConvNeXt V2) of an NHWC bf16 tensor,
+    NHWC out: ``weight * (x * Nx) + bias + x`` with ``Nx`` each (image,
+    channel) plane's L2 norm over the mean of the image's norms plus ``eps``.
+    fp32 ``weight`` / ``bias``, zero at the start as in the paper;
+    ``num_channels % 8 == 0``, at most 4096 (:data:`flashy_amd.ops.GRN_RULE`).
+    """
+
+    def __init__(self, num_channels: int, eps: float = 1e-6):
+        super().__init__()
+        if num_channels < 8 or num_channels % 8 or num_channels > 4096:
+            raise ValueError(f"{ops.GRN_RULE}; got {num_channels} channels")
+        self.num_channels = num_channels
+        self.eps = eps
+        self.weight = nn.Parameter(torch.zeros(num_channels))
+        self.bias = nn.Parameter(torch.zeros(num_channels))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return _GrnFn.apply(x, self.weight, self.bias, self.eps)
+
+
+class _BiasGeluGrnFn(torch.autograd.Function):
+    """grn(gelu(h + bias)): the GELU walk gathers GRN's sums of squares, so
+    ``g`` is not read again for them.  ``g`` is kept, not recomputed: GRN's
+    backward reads it."""
+
+    @staticmethod
+    def forward(ctx, h: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor,
+                beta: torch.Tensor, eps: float):
+        h = h.contiguous()
+        g, out = torch.empty_like(h), torch.empty_like(h)
+        nx, a, rden = _grn_coefs(h)
+        plan = ops.grn_plan(h.shape[0], h.numel() // (h.shape[0] * h.shape[-1]),
+                            h.shape[-1])
+        sq = torch.empty(h.shape[0], plan.slices, h.shape[-1],
+                         dtype=torch.float32, device=h.device)
+        ops.bias_gelu_sqsum(h, bias, g, sq)
+        ops.grn_fwd(g, gamma, beta, out, nx, a, rden, eps, sq)
+        ctx.save_for_backward(h, g, nx, a, rden)
+        ctx.refs = (bias, gamma, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        h, g, nx, a, rden = ctx.saved_tensors
+        bias, gamma, beta = ctx.refs
+        (db, dgamma, dbeta), grads = _param_grads(ctx, (bias, gamma, beta), 1)
+        dg, dh = torch.empty_like(g), torch.empty_like(h)
+        ops.grn_bwd(dout.contiguous(), g, nx, a, rden, gamma, dg, dgamma,
+                    dbeta)
+        ops.bias_gelu_bwd(dg, h, bias, dh, db)
+        return (dh, *grads, None)
+
+
+def bias_gelu_grn(h: torch.Tensor, bias: torch.Tensor,
+                  grn: GRN) -> torch.Tensor:
+    """``grn(gelu(h + bias))`` over NHWC bf16 ``h`` with an fp32 per-channel
+    ``bias``: the fused GELU + sum-of-squares forward, then GRN's coefficient
+    and apply kernels.  Backward is GRN's followed by that of
+    :func:`bias_gelu`."""
+    return _BiasGeluGrnFn.apply(h, bias, grn.weight, grn.bias, grn.eps)

@@ -1367,6 +1367,132 @@ def scale_residual_bwd(dout: torch.Tensor, z: torch.Tensor, b: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# global response normalization (csrc/grn.hip).  Activations are contiguous
+# NHWC bf16 [N, ..., C] (HW = the product of the dims between); gamma, beta
+# and their gradients are fp32 [C]; the saved coefficients ``nx`` and ``a``
+# are fp32 [N, C], ``rden`` (1 / (mu + eps)) fp32 [N].  Gradient targets are
+# ACCUMULATED into; a None target is skipped.
+# ---------------------------------------------------------------------------
+
+GRN_RULE = ("global response normalization needs NHWC activations [N, ..., C] "
+            "with C % 8 == 0 and 8 <= C <= 4096, at least one image of at "
+            "least one pixel")
+
+
+class GrnPlan(tp.NamedTuple):
+    served: int
+    lanes: int           # lanes per row
+    rows_per_block: int
+    slices: int          # fp32 slices per image: grid.x of the walk kernels
+    col_chunks: int      # grid.z of the walk kernels
+    grid: tp.Tuple[int, int, int]   # the walk kernels'; coef runs on (N,)
+
+
+def grn_plan(N: int, HW: int, C: int) -> GrnPlan:
+    """What csrc/grn.hip decides for ``[N, HW, C]`` (dims only)."""
+    served, lanes, rpb, slices, chunks = require().grn_plan(N, HW, C)
+    return GrnPlan(served, lanes, rpb, slices, chunks,
+                   (slices, min(N, 65535), chunks))
+
+
+def _grn_check(name: str, acts: tp.Sequence[torch.Tensor],
+               params: tp.Sequence[tp.Optional[torch.Tensor]],
+               coefs: tp.Sequence[torch.Tensor] = (),
+               rden: tp.Optional[torch.Tensor] = None,
+               sq: tp.Optional[torch.Tensor] = None
+               ) -> tp.Tuple[int, int, int]:
+    """Shapes, dtypes and layouts are refused here before the extension is
+    loaded; the size of a workspace ``sq`` of sums of squares is held to
+    :func:`grn_plan` before any launch.  Returns (N, HW, C)."""
+    x = acts[0]
+    N = x.shape[0] if x.dim() >= 2 else 0
+    C = x.shape[-1] if x.dim() >= 2 else 0
+    HW = x.numel() // (N * C) if N and C else 0
+    if (N < 1 or HW < 1 or C < 8 or C % 8 or C > 4096 or N >= 2 ** 31
+            or HW >= 2 ** 31):
+        raise ValueError(f"{name}: {GRN_RULE}; got shape {tuple(x.shape)}")
+    for t in acts:
+        assert t.dtype == torch.bfloat16, f"{name}: activations are bf16"
+        assert t.is_contiguous(), f"{name}: activations are contiguous"
+        assert t.shape == x.shape, (t.shape, x.shape)
+        assert t.data_ptr() % 16 == 0, "16-byte lanes need an aligned tensor"
+    for p in params:
+        if p is not None:
+            assert p.dtype == torch.float32 and p.is_contiguous()
+            assert p.numel() == C, (p.shape, C)
+    for t, n in [(t, N * C) for t in coefs] + [(rden, N)]:
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_contiguous()
+            assert t.numel() == n, f"{name}: a coefficient array of {n}"
+    if sq is not None:
+        slices = grn_plan(N, HW, C).slices
+        assert sq.dtype == torch.float32 and sq.is_contiguous()
+        assert sq.numel() == N * slices * C, \
+            f"{name}: the workspace holds [N, {slices}, C] fp32 (ops.grn_plan)"
+    for t in (*acts, *params, *coefs, rden, sq):
+        assert t is None or (t.is_cuda and t.device == x.device), \
+            f"{name}: every tensor lives on one GPU"
+    return N, HW, C
+
+
+def grn_sqsum(x: torch.Tensor, sq: torch.Tensor) -> None:
+    """``sq`` (fp32 [N, slices, C], slices from :func:`grn_plan`) receives the
+    per-image column sums of x^2, one slice per walk block."""
+    N, HW, C = _grn_check("grn_sqsum", [x], [], sq=sq)
+    require().grn_sqsum(x.data_ptr(), sq.data_ptr(), N, HW, C, _stream())
+
+
+def bias_gelu_sqsum(h: torch.Tensor, b: torch.Tensor, g: torch.Tensor,
+                    sq: torch.Tensor) -> None:
+    """g = gelu(h + b), bitwise :func:`bias_gelu_fwd`'s, and on the same walk
+    ``sq`` = what :func:`grn_sqsum` gives on that g, bitwise."""
+    N, HW, C = _grn_check("bias_gelu_sqsum", [h, g], [b], sq=sq)
+    require().bias_gelu_sqsum(h.data_ptr(), b.data_ptr(), g.data_ptr(),
+                              sq.data_ptr(), N, HW, C, _stream())
+
+
+def grn_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+            out: torch.Tensor, nx: torch.Tensor, a: torch.Tensor,
+            rden: torch.Tensor, eps: float,
+            sq: tp.Optional[torch.Tensor] = None) -> None:
+    """out = gamma * (x * Nx) + beta + x with Nx = Gx / (mean_c Gx + eps),
+    Gx the L2 norm of each (image, channel) plane.  ``nx``, ``a`` and ``rden``
+    receive Nx, 1 + gamma * Nx and 1 / (mean_c Gx + eps): what
+    :func:`grn_bwd` needs besides ``x``.  ``sq``: the sums of squares of ``x``
+    where :func:`bias_gelu_sqsum` has gathered them already."""
+    N, HW, C = _grn_check("grn_fwd", [x, out], [gamma, beta], [nx, a], rden,
+                          sq)
+    if sq is None:
+        sq = torch.empty(N, grn_plan(N, HW, C).slices, C, dtype=torch.float32,
+                         device=x.device)
+        require().grn_sqsum(x.data_ptr(), sq.data_ptr(), N, HW, C, _stream())
+    require().grn_fwd(x.data_ptr(), sq.data_ptr(), gamma.data_ptr(),
+                      beta.data_ptr(), out.data_ptr(), nx.data_ptr(),
+                      a.data_ptr(), rden.data_ptr(), N, HW, C, float(eps),
+                      _stream())
+
+
+def grn_bwd(dout: torch.Tensor, x: torch.Tensor, nx: torch.Tensor,
+            a: torch.Tensor, rden: torch.Tensor, gamma: torch.Tensor,
+            dx: tp.Optional[torch.Tensor], dgamma: tp.Optional[torch.Tensor],
+            dbeta: tp.Optional[torch.Tensor]) -> None:
+    """Backward of :func:`grn_fwd` from its input and saved coefficients:
+    writes ``dx`` (unless None) and adds sum_n Nx * sum_hw dout * x and
+    sum dout into ``dgamma`` / ``dbeta``.  Deterministic: no atomics."""
+    N, HW, C = _grn_check("grn_bwd",
+                          [dout, x] + ([dx] if dx is not None else []),
+                          [gamma, dgamma, dbeta], [nx, a], rden)
+    slices = grn_plan(N, HW, C).slices
+    ws = torch.empty(N * (slices + 1) * 2 + N, C, dtype=torch.float32,
+                     device=x.device)
+    pq, b = ws[N * slices * 2:N * (slices + 1) * 2], ws[N * (slices + 1) * 2:]
+    require().grn_bwd(dout.data_ptr(), x.data_ptr(), nx.data_ptr(),
+                      a.data_ptr(), rden.data_ptr(), gamma.data_ptr(),
+                      _ptr(dx), ws.data_ptr(), pq.data_ptr(), b.data_ptr(),
+                      _ptr(dgamma), _ptr(dbeta), N, HW, C, _stream())
+
+
+# ---------------------------------------------------------------------------
 # batchnorm kernels (NHWC training BN; see flashy_amd/nn.py)
 # ---------------------------------------------------------------------------
 

@@ -111,6 +111,18 @@ int launch_scale_residual_fwd(const void* z, const void* b, const void* s,
 int launch_scale_residual_bwd(const void* dout, const void* z, const void* b,
                               const void* s, void* dz, void* ws, void* ds,
                               void* db, int M, int C, hipStream_t stream);
+int grn_plan(int N, int HW, int C, int* out);
+int launch_grn_sqsum(const void* x, void* ws, int N, int HW, int C,
+                     hipStream_t stream);
+int launch_bias_gelu_sqsum(const void* h, const void* b, void* out, void* ws,
+                           int N, int HW, int C, hipStream_t stream);
+int launch_grn_fwd(const void* x, const void* ws, const void* gamma,
+                   const void* beta, void* out, void* nx, void* a, void* rden,
+                   int N, int HW, int C, float eps, hipStream_t stream);
+int launch_grn_bwd(const void* dout, const void* x, const void* nx,
+                   const void* a, const void* rden, const void* gamma,
+                   void* dx, void* ws, void* pq, void* b, void* dgamma,
+                   void* dbeta, int N, int HW, int C, hipStream_t stream);
 void launch_bn_stats(const void* x, void* partials, int64_t M, int C,
                      int msplit, hipStream_t stream);
 void launch_bn_finalize(const void* partials, int msplit, const void* gamma,
@@ -721,6 +733,57 @@ PYBIND11_MODULE(_hip_ops, m) {
                                              as_stream(stream)))
                   throw std::invalid_argument(
                       "scale_residual_bwd: unsupported shape");
+              check_last();
+          });
+    // Global response normalization (csrc/grn.hip): the plan's (served, lanes
+    // per row, rows per block, slices per image, column chunks); a 0 pointer
+    // is a gradient nobody wants
+    m.def("grn_plan", [](int N, int HW, int C) {
+        int p[4];
+        const int served = grn_plan(N, HW, C, p);
+        return py::make_tuple(served, p[0], p[1], p[2], p[3]);
+    });
+    m.def("grn_sqsum",
+          [](uintptr_t x, uintptr_t ws, int N, int HW, int C,
+             uintptr_t stream) {
+              if (!launch_grn_sqsum((const void*)x, (void*)ws, N, HW, C,
+                                    as_stream(stream)))
+                  throw std::invalid_argument("grn_sqsum: unsupported shape");
+              check_last();
+          });
+    m.def("bias_gelu_sqsum",
+          [](uintptr_t h, uintptr_t b, uintptr_t out, uintptr_t ws, int N,
+             int HW, int C, uintptr_t stream) {
+              if (!launch_bias_gelu_sqsum((const void*)h, (const void*)b,
+                                          (void*)out, (void*)ws, N, HW, C,
+                                          as_stream(stream)))
+                  throw std::invalid_argument(
+                      "bias_gelu_sqsum: unsupported shape");
+              check_last();
+          });
+    m.def("grn_fwd",
+          [](uintptr_t x, uintptr_t ws, uintptr_t gamma, uintptr_t beta,
+             uintptr_t out, uintptr_t nx, uintptr_t a, uintptr_t rden, int N,
+             int HW, int C, float eps, uintptr_t stream) {
+              if (!launch_grn_fwd((const void*)x, (const void*)ws,
+                                  (const void*)gamma, (const void*)beta,
+                                  (void*)out, (void*)nx, (void*)a, (void*)rden,
+                                  N, HW, C, eps, as_stream(stream)))
+                  throw std::invalid_argument("grn_fwd: unsupported shape");
+              check_last();
+          });
+    m.def("grn_bwd",
+          [](uintptr_t dout, uintptr_t x, uintptr_t nx, uintptr_t a,
+             uintptr_t rden, uintptr_t gamma, uintptr_t dx, uintptr_t ws,
+             uintptr_t pq, uintptr_t b, uintptr_t dgamma, uintptr_t dbeta,
+             int N, int HW, int C, uintptr_t stream) {
+              if (!launch_grn_bwd((const void*)dout, (const void*)x,
+                                  (const void*)nx, (const void*)a,
+                                  (const void*)rden, (const void*)gamma,
+                                  (void*)dx, (void*)ws, (void*)pq, (void*)b,
+                                  (void*)dgamma, (void*)dbeta, N, HW, C,
+                                  as_stream(stream)))
+                  throw std::invalid_argument("grn_bwd: unsupported shape");
               check_last();
           });
     m.def("bn_stats",

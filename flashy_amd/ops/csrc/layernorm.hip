@@ -69,11 +69,8 @@
 // trades slice traffic (2 / rpb of the activation bytes) against filling the
 // chip at small M.
 
-#include "common.h"
+#include "rowops.h"
 
-#define LN_THREADS 256
-#define LN_MAXG 64              // lanes of a group, at most one wave
-#define LN_CHUNK 512            // channels of one elementwise column chunk
 #define LN_BLOCKS 1024          // row blocks aimed at: 4 per CU of 256
 #define LN_MINROWS 16           // floor on rows per block
 #define LN_RUNS 8               // combine: runs of slices summed side by side
@@ -128,13 +125,6 @@ static bool ln_geom(int M, int C, bool layernorm, LnGeom* g, dim3* grid,
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 
-// what __syncthreads expands to
-__device__ __forceinline__ void ln_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // sum over the G lanes of this lane's group; every lane gets the same bits
 __device__ __forceinline__ float ln_group_sum(float v, int lane, int G) {
     for (int off = G >> 1; off > 0; off >>= 1) {
@@ -169,53 +159,6 @@ __device__ __forceinline__ float ln_group_sum2(float hi, float lo, int lane,
         lo = (lo + ol) + r;
     }
     return hi + lo;
-}
-
-__device__ __forceinline__ void ln_load8(const uint16_t* __restrict__ p,
-                                         int64_t at, float f[8]) {
-    const short8 v = *reinterpret_cast<const short8*>(p + at);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) f[c] = bf16_to_f32((uint16_t)v[c]);
-}
-
-__device__ __forceinline__ void ln_store8(uint16_t* __restrict__ p, int64_t at,
-                                          const float f[8]) {
-    short8 v;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) v[c] = (short)f32_to_bf16(f[c]);
-    *reinterpret_cast<short8*>(p + at) = v;
-}
-
-// 8 fp32 parameters at channel ch; `fill` where the lane is idle or the
-// parameter is absent.  Scalar loads: a parameter may be a 4-byte aligned
-// view into a flat arena, and this runs once per block.
-__device__ __forceinline__ void ln_param8(const float* __restrict__ p, int ch,
-                                          bool on, float fill, float f[8]) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) f[c] = (on && p) ? p[ch + c] : fill;
-}
-
-// Phi(u) (normal CDF) and phi(u) (density); gelu(u) = u * Phi(u)
-__device__ __forceinline__ void ln_gauss(float u, float* Phi, float* phi) {
-    const float z = __builtin_fabsf(u) * 0.70710678f;
-    const float t = 1.f / __builtin_fmaf(0.3275911f, z, 1.f);
-    // exp(-u^2 / 2) with the rounding of the square put back
-    const float sq = u * u;
-    const float e = __builtin_expf(-0.5f * sq) *
-                    __builtin_fmaf(-0.5f, __builtin_fmaf(u, u, -sq), 1.f);
-    float poly = 5.750628480e-02f;
-    poly = __builtin_fmaf(poly, t, -3.215564865e-01f);
-    poly = __builtin_fmaf(poly, t, 6.375867681e-01f);
-    poly = __builtin_fmaf(poly, t, -5.734744838e-01f);
-    poly = __builtin_fmaf(poly, t, 5.123662973e-01f);
-    poly = __builtin_fmaf(poly, t, -5.620583739e-02f);
-    poly = __builtin_fmaf(poly, t, 2.079440067e-01f);
-    poly = __builtin_fmaf(poly, t, 1.652116966e-01f);
-    poly = __builtin_fmaf(poly, t, 1.858453488e-01f);
-    poly = __builtin_fmaf(poly, t, 1.847764033e-01f);
-    const float tail = 0.5f * poly * t * e;        // 0.5 * erfc(|z|)
-    *Phi = u < 0.f ? tail : 1.f - tail;
-    *phi = 0.39894228f * e;
 }
 
 // The walk of one thread: its group lane, its row slot and its octets.
@@ -587,8 +530,8 @@ k_colsum_combine(const float* __restrict__ ws, float* __restrict__ d0,
 #endif
 
 // ---------------------------------------------------------------------------
-static void ln_combine(const void* ws, void* d0, void* d1, void* d2, int k,
-                       int C, int slices, hipStream_t stream) {
+void ln_combine(const void* ws, void* d0, void* d1, void* d2, int k, int C,
+                int slices, hipStream_t stream) {
     const int blocks = (k * C + LN_RCOLS - 1) / LN_RCOLS;
     k_colsum_combine<<<blocks, LN_THREADS, 0, stream>>>(
         (const float*)ws, (float*)d0, (float*)d1, (float*)d2, k, C, slices);
