@@ -662,14 +662,16 @@ def _splitk_plan(M: int, ktiles: int, red_stages: int):
 
 def _underfill_zn(M: int, channels: int, stages: int) -> int:
     """Under-fill forcing for small-M long-reduction layers (r4-class): the
-    8-wave grid of 256-row tiles underfills the chip without a K split, so
-    slice the reduction until ~160 blocks exist and the 8-wave split-K
-    launcher engages.  ``channels`` is the GEMM column count (K for fwd, C
-    for dgrad).  Returns zn (0 = leave it single pass)."""
+    8-wave grid underfills the chip without a K split, so slice the
+    reduction until ~160 blocks exist and the 8-wave split-K launcher
+    engages.  The column tile and the rows per block to count are the native
+    plan's (conv8.h says why the count is not always the running tile's).
+    ``channels`` is the GEMM column count (K for fwd, C for dgrad).  Returns
+    zn (0 = leave it single pass)."""
     if stages < 16:
         return 0
-    bn8 = 128 if channels % 128 == 0 else 64
-    tiles8 = ((M + 255) // 256) * (channels // bn8)
+    _, bn8, rows8 = require().conv8_splitk_tile(M, channels)
+    tiles8 = ((M + rows8 - 1) // rows8) * (channels // bn8)
     if not tiles8 or tiles8 >= 160:
         return 0
     zn = min(max(2, -(-160 // tiles8)), 8, stages // 8)
@@ -834,7 +836,34 @@ def splitk_combine(ws: torch.Tensor, out: torch.Tensor, zn: int,
                              _stream())
 
 
-DGRAD_S2_FORMS = {"generic": 0, "par8": 1, "par4": 2, "scat2": 3}
+DGRAD_S2_FORMS = {"generic": 0, "par8": 1, "par4": 2, "scat2": 3,
+                  "par8m128": 4}
+
+
+def conv8_form(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor,
+               d: ConvDims, dgrad: bool, bm: int, bn: int, spz: int = 0,
+               bn_ws: tp.Optional[torch.Tensor] = None) -> int:
+    """One 8-wave kernel through a named tile, whatever the plan would pick
+    (tests and scripts/splitk_sweep.py): forward (``a`` = x, ``w`` KRSC) or
+    backward-data (``a`` = dy, ``w`` RSCK) at ``bm`` x ``bn``.  ``spz == 0``
+    is a single pass into the bf16 ``out``, with BN partials
+    ``[2][K][msplit]`` into ``bn_ws`` (forward only; msplit is returned);
+    ``spz > 0`` writes split-K slices of ``spz`` stages into the fp32 slab
+    ``out`` ``[zeff][M][cols]``.  Raises where the tile cannot run."""
+    M = d.N * d.H * d.W if dgrad else d.N * d.Ho * d.Wo
+    cols = d.C if dgrad else d.K
+    stages = d.R * d.S * (d.K if dgrad else d.C) // 64
+    zeff = (stages + spz - 1) // spz if spz else 1
+    want = torch.float32 if spz else torch.bfloat16
+    assert out.dtype == want and out.numel() >= zeff * M * cols, \
+        (out.dtype, out.numel(), zeff, M, cols)
+    if bn_ws is not None:
+        assert not dgrad and not spz and bn_ws.dtype == torch.float32
+        assert bn_ws.numel() >= 2 * d.K * ((M + bm - 1) // bm)
+    return require().conv8_form(
+        dgrad, a.data_ptr(), w.data_ptr(), out.data_ptr(),
+        bn_ws.data_ptr() if bn_ws is not None else 0, *d, bm, bn, spz,
+        _stream())
 
 
 def conv_dgrad_s2_plan(d: ConvDims) -> tp.Tuple[str, int]:
@@ -851,7 +880,8 @@ def conv_dgrad_s2_form(dout: torch.Tensor, w_rsck: torch.Tensor,
                        tile: int) -> None:
     """Stride-2 dgrad through one named form, whatever the plan would pick
     (tests and scripts/dgrad_s2_sweep.py): "par8" / "par4" / "scat2" as in
-    :func:`conv_dgrad_s2_plan`, or "generic" (the zero-filled single-pass
+    :func:`conv_dgrad_s2_plan`, "par8m128" (the 8-wave parity classes in
+    128-row tiles, tile = BN), or "generic" (the zero-filled single-pass
     kernels, ``tile`` ignored); raises where the form cannot run the shape."""
     require().conv_dgrad_s2_form(dout.data_ptr(), w_rsck.data_ptr(),
                                  dx.data_ptr(), *d, DGRAD_S2_FORMS[form],

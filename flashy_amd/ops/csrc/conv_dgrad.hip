@@ -228,17 +228,21 @@ extern "C" int conv_dgrad_s2_plan(ConvDims d, int* tile_out) {
         // it is write-bound already (9.2 us at 64 <- 128, every other form
         // slower); where it has not, 32-row parity tiles — class 0 is the
         // quarter GEMM, the three tapless classes store zeros
-        int bn8;
+        Tile8 t8;
         *tile_out = 0;
-        if (conv_dgrad8_plan(d, &bn8) || !par4_32) return DGRAD_S2_NONE;
+        if (conv_dgrad8_plan(d, &t8) || !par4_32) return DGRAD_S2_NONE;
         *tile_out = 32;
         return DGRAD_S2_PAR4;
     }
     // the four classes run 4:2:2:1 stages (3x3), so blocks of the short
     // classes retire early: the 8-wave form needs its floor in class blocks
-    const int mt8 = conv8_disabled() ? 0 : conv_dgrad8_par2_mtiles(d);
-    if (mt8 && pick_bn8(mt8 * 4, d.C, kPar8Floor, tile_out))
+    // (128-row class tiles run by name only: profiles/README.md, r08a)
+    Tile8 t8;
+    if (!conv8_disabled() && conv_dgrad8_par2_mtiles(d, 256) &&
+        pick_tile8(Mc, d.C, kPar8Floor, &t8, 4)) {
+        *tile_out = t8.bn;
         return DGRAD_S2_PAR8;
+    }
     if (!par4_32) return DGRAD_S2_NONE;   // generic, split-K allowed
     // under that floor 32-row tiles beat 64 and 128 at every measured shape
     // (most blocks); 128 / 64 are for the 8-wave family switched off
@@ -263,10 +267,12 @@ extern "C" int launch_conv_dgrad_s2_form(const void* dout, const void* w_rsck,
         return 1;
     }
     if (d.stride != 2 || d.C % 64 || d.K % 64) return 0;
-    if (form == DGRAD_S2_PAR8) {
-        const int mt = conv_dgrad8_par2_mtiles(d);
+    if (form == DGRAD_S2_PAR8 || form == DGRAD_S2_PAR8_M128) {
+        const int bm = form == DGRAD_S2_PAR8 ? 256 : 128;
+        const int mt = conv_dgrad8_par2_mtiles(d, bm);
         if (!mt || (tile != 64 && tile != 128) || d.C % tile) return 0;
-        launch_conv_dgrad8_par2(dout, w_rsck, dx, d, tile, mt, stream);
+        launch_conv_dgrad8_par2(dout, w_rsck, dx, d, Tile8{bm, tile}, mt,
+                                stream);
         return 1;
     }
     if (form == DGRAD_S2_PAR4) {
@@ -318,10 +324,10 @@ static void launch_conv_dgrad_generic(const void* dout, const void* w_rsck,
         }
     }
     {
-        int bn8;
-        const int mt8 = conv_dgrad8_plan(d, &bn8);
+        Tile8 t8;
+        const int mt8 = conv_dgrad8_plan(d, &t8);
         if (mt8) {
-            launch_conv_dgrad8(dout, w_rsck, dx, d, bn8, mt8, stream);
+            launch_conv_dgrad8(dout, w_rsck, dx, d, t8, mt8, stream);
             return;
         }
     }
@@ -365,10 +371,10 @@ extern "C" void launch_conv_dgrad_splitk(const void* dout, const void* w_rsck,
     // 8-wave split-K for the small-M long-reduction layers (r4-class)
     if (d.C % 64 == 0 && d.K % 64 == 0 && rsk % 64 == 0 &&
         (int64_t)d.N * d.Ho * d.Wo * d.K * 2 < (int64_t)kOobSentinel) {
-        const int mtiles = (int)((M + 255) / 256);
-        const int bn8 = d.C % 128 == 0 ? 128 : 64;
-        if ((int64_t)mtiles * (d.C / bn8) * zeff >= 120) {
-            launch_conv_dgrad8_splitk(dout, w_rsck, ws, d, bn8, mtiles, spz,
+        const Tile8 t = splitk_tile8(M, d.C);
+        if (blocks8(M, d.C, t) * zeff >= kSplitkFloor8) {
+            launch_conv_dgrad8_splitk(dout, w_rsck, ws, d, t,
+                                      (int)((M + t.bm - 1) / t.bm), spz,
                                       zeff, stream);
             return;
         }

@@ -32,23 +32,26 @@
 // reaches (R or S == 1) runs no stage and stores zeros.  Instantiated with
 // S1 = true (ho = hb - r' needs no division).
 template <int BN, bool S1, bool SCAT2 = false, bool SPLITK = false,
-          bool PAR2 = false>
+          bool PAR2 = false, int BM = 256>
 __global__ void __launch_bounds__(512, 2)
 k_conv_dgrad8(const uint16_t* __restrict__ dout,
               const uint16_t* __restrict__ w_rsck,
               uint16_t* __restrict__ dx, ConvDims d, unsigned dout_nbytes,
               int spz = 0) {
-    constexpr int BM = 256;
+    static_assert(BM == 256 || (BM == 128 && !SCAT2),
+                  "8 waves as 2(M) x 4(N); SCAT2 has 256-row tiles only");
     constexpr int BK = 64;
     constexpr int NF = BN / 64;
-    constexpr int MF = 8;
+    constexpr int MF = BM / 32;
+    constexpr int AG = BM / 64;          // A glds per wave per stage
     constexpr int A_ELEMS = BM * BK;
     constexpr int B_ELEMS = BN * BK;
     constexpr int BUF_ELEMS = A_ELEMS + B_ELEMS;
-    constexpr int G = 4 + BN / 64;       // glds per wave per stage (A + B)
-    // BN=64 buffers fit 4x in the 160 KiB LDS -> prefetch DEPTH 2 (two
-    // stages' DMA in flight across barriers); BN=128 fits 3 -> depth 1
-    constexpr int BUFS = BN == 64 ? 4 : 3;
+    constexpr int G = AG + BN / 64;      // glds per wave per stage (A + B)
+    // BM=256: BN=64 buffers fit 4x in the 160 KiB LDS -> prefetch DEPTH 2
+    // (two stages' DMA in flight across barriers); BN=128 fits 3 -> depth 1.
+    // BM=128 buffers are 24 / 32 KiB: 4 of them, depth 2 (see conv_fwd8.hip)
+    constexpr int BUFS = (BN == 64 || BM == 128) ? 4 : 3;
     constexpr int DEPTH = BUFS - 2;
 
     // PAR2 class geometry: first input coordinate (a0, b0), extents (Hc, Wc)
@@ -82,11 +85,11 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
     const auto arsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)dout, 0, dout_nbytes, 0x00020000);
 
-    // A: 4 dest chunks/thread; (r,s,k) walks +BK per stage.
-    int a_r[4], a_s[4], a_k[4], a_hi[4], a_wi[4];
-    int64_t a_n[4];
+    // A: AG dest chunks/thread; (r,s,k) walks +BK per stage.
+    int a_r[AG], a_s[AG], a_k[AG], a_hi[AG], a_wi[AG];
+    int64_t a_n[AG];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
+    for (int g = 0; g < AG; ++g) {
         const int chunk = g * 512 + tid;
         const int row = chunk >> 3;
         const int kc_s = (chunk & 7) ^ (row & 7);
@@ -131,7 +134,7 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
     auto issue_stage = [&](int buf) {
         uint16_t* base = lds + buf * BUF_ELEMS;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
+        for (int g = 0; g < AG; ++g) {
             unsigned voff = kOobSentinel;
             if (SCAT2) {
                 if (a_n[g] >= 0)
@@ -185,7 +188,7 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
         }
     };
 
-    const int a_row_l = wave_m * 128 + (lane & 15);
+    const int a_row_l = wave_m * (BM / 2) + (lane & 15);
     const int frag_kb = (lane >> 4) * 16;
     const int b_col_l = wave_n * (BN / 4) + (lane & 15);
 
@@ -251,7 +254,7 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
         compute_stage((n_stages - 1) % BUFS);
     }
 
-    const int64_t out_row0 = m0 + wave_m * 128 + (lane & 15);
+    const int64_t out_row0 = m0 + wave_m * (BM / 2) + (lane & 15);
     const int out_col0 = col0 + wave_n * (BN / 4) + (lane >> 4) * 4;
     if (SPLITK) {   // fp32 partials slab [z][M][C]
         float* ws = reinterpret_cast<float*>(dx);
@@ -309,14 +312,14 @@ k_conv_dgrad8(const uint16_t* __restrict__ dout,
     }
 }
 
-extern "C" int conv_dgrad8_plan(ConvDims d, int* bn_out) {
+extern "C" int conv_dgrad8_plan(ConvDims d, Tile8* tile_out) {
     if (conv8_disabled()) return 0;
     const int64_t M = (int64_t)d.N * d.H * d.W;
     if (d.C % 64 || d.K % 64) return 0;
     const int64_t dout_elems = (int64_t)d.N * d.Ho * d.Wo * d.K;
     if (dout_elems * 2 >= (int64_t)kOobSentinel) return 0;
-    const int mtiles = (int)((M + 255) / 256);
-    return pick_bn8(mtiles, d.C, 160, bn_out) ? mtiles : 0;
+    if (!pick_tile8(M, d.C, kFloor8, tile_out)) return 0;
+    return (int)((M + tile_out->bm - 1) / tile_out->bm);
 }
 
 // SCAT2 grid.x (0 = the shape cannot take it): 1x1 stride 2, even H/W
@@ -347,54 +350,59 @@ extern "C" int conv_dgrad8_s2_plan(ConvDims d, int* bn_out) {
 
 // The launchers differ only in SCAT2 / SPLITK / PAR2; S1 follows the stride
 // (SCAT2 reads dy linearly and ignores it, PAR2 walks its class at stride 1).
+// SCAT2 has 256-row tiles only (smaller grids measured slower, TODO.md).
 template <bool SCAT2_LAUNCH, bool SPLITK, bool PAR2 = false>
 static void launch_dgrad8(const void* dout, const void* w_rsck, void* out,
-                          ConvDims d, int bn, int mtiles, int spz, int zeff,
-                          hipStream_t stream) {
-    dim3 grid((unsigned)mtiles, (unsigned)(d.C / bn), (unsigned)zeff);
+                          ConvDims d, Tile8 tile, int mtiles, int spz,
+                          int zeff, hipStream_t stream) {
+    dim3 grid((unsigned)mtiles, (unsigned)(d.C / tile.bn), (unsigned)zeff);
     const unsigned db = (unsigned)((int64_t)d.N * d.Ho * d.Wo * d.K * 2);
-    dispatch8(bn, PAR2 || d.stride == 1, [&](auto BN, auto S1) {
+    dispatch8(tile, PAR2 || d.stride == 1,
+              [&](auto BM, auto BN, auto S1) {
         constexpr bool s1 = PAR2 || (!SCAT2_LAUNCH && decltype(S1)::value);
-        k_conv_dgrad8<decltype(BN)::value, s1, SCAT2_LAUNCH, SPLITK, PAR2>
+        constexpr int bm = SCAT2_LAUNCH ? 256 : decltype(BM)::value;
+        k_conv_dgrad8<decltype(BN)::value, s1, SCAT2_LAUNCH, SPLITK, PAR2, bm>
             <<<grid, 512, 0, stream>>>((const uint16_t*)dout,
                                        (const uint16_t*)w_rsck,
                                        (uint16_t*)out, d, db, spz);
     });
 }
 
-// 8-wave parity-class grid.x: 256-row tiles of the largest class
-extern "C" int conv_dgrad8_par2_mtiles(ConvDims d) {
+// 8-wave parity-class grid.x: bm-row tiles of the largest class
+extern "C" int conv_dgrad8_par2_mtiles(ConvDims d, int bm) {
     if (d.stride != 2 || d.C % 64 || d.K % 64) return 0;
     const int64_t dout_elems = (int64_t)d.N * d.Ho * d.Wo * d.K;
     if (dout_elems * 2 >= (int64_t)kOobSentinel) return 0;
     const int64_t Mc = (int64_t)d.N * ((d.H + 1) / 2) * ((d.W + 1) / 2);
-    return (int)((Mc + 255) / 256);
+    return (int)((Mc + bm - 1) / bm);
 }
 
 extern "C" void launch_conv_dgrad8_par2(const void* dout, const void* w_rsck,
-                                        void* dx, ConvDims d, int bn,
+                                        void* dx, ConvDims d, Tile8 tile,
                                         int mtiles, hipStream_t stream) {
-    launch_dgrad8<false, false, true>(dout, w_rsck, dx, d, bn, mtiles, 0, 4,
+    launch_dgrad8<false, false, true>(dout, w_rsck, dx, d, tile, mtiles, 0, 4,
                                       stream);
 }
 
 extern "C" void launch_conv_dgrad8_s2(const void* dout, const void* w_rsck,
                                       void* dx, ConvDims d, int bn,
                                       int mtiles, hipStream_t stream) {
-    launch_dgrad8<true, false>(dout, w_rsck, dx, d, bn, mtiles, 0, 1, stream);
+    launch_dgrad8<true, false>(dout, w_rsck, dx, d, Tile8{256, bn}, mtiles, 0,
+                               1, stream);
 }
 
 extern "C" void launch_conv_dgrad8(const void* dout, const void* w_rsck,
-                                   void* dx, ConvDims d, int bn, int mtiles,
-                                   hipStream_t stream) {
-    launch_dgrad8<false, false>(dout, w_rsck, dx, d, bn, mtiles, 0, 1, stream);
+                                   void* dx, ConvDims d, Tile8 tile,
+                                   int mtiles, hipStream_t stream) {
+    launch_dgrad8<false, false>(dout, w_rsck, dx, d, tile, mtiles, 0, 1,
+                                stream);
 }
 
 extern "C" void launch_conv_dgrad8_splitk(const void* dout,
                                           const void* w_rsck, void* ws,
-                                          ConvDims d, int bn, int mtiles,
+                                          ConvDims d, Tile8 tile, int mtiles,
                                           int spz, int zeff,
                                           hipStream_t stream) {
-    launch_dgrad8<false, true>(dout, w_rsck, ws, d, bn, mtiles, spz, zeff,
+    launch_dgrad8<false, true>(dout, w_rsck, ws, d, tile, mtiles, spz, zeff,
                                stream);
 }

@@ -386,6 +386,7 @@ enum FwdPath { FWD_DEDUP, FWD_MLOOP, FWD_8WAVE, FWD_TILE4 };
 struct ConvFwdPlan {
     FwdPath path;
     int bn, gridx;
+    Tile8 tile8;                  // 8-wave tile
     int msplit;                   // slices of the fused BN-stats partials
     int tpi, rows, lds_elems;     // dedup
     int mtiles;                   // mloop (gridx blocks walk mtiles tiles)
@@ -400,9 +401,9 @@ static ConvFwdPlan conv_fwd_plan(ConvDims d) {
     } else if ((p.mtiles = conv1x1_mloop_plan(d, &p.bn, &p.gridx))) {
         p.path = FWD_MLOOP;
         p.msplit = 2 * p.mtiles;   // per-(tile, wave_m) slices
-    } else if ((p.gridx = conv_fwd8_plan(d, &p.bn))) {
+    } else if ((p.gridx = conv_fwd8_plan(d, &p.tile8))) {
         p.path = FWD_8WAVE;
-        p.msplit = p.gridx;
+        p.msplit = p.gridx;        // one partial per (bm-row) tile
     } else {
         const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
         p.path = FWD_TILE4;
@@ -430,7 +431,7 @@ extern "C" void launch_conv_fwd(const void* x, const void* w, void* y,
                              p.mtiles, stream);
         return;
     case FWD_8WAVE:
-        launch_conv_fwd8(x, w, y, d, relu, bn_ws, p.bn, p.gridx, stream);
+        launch_conv_fwd8(x, w, y, d, relu, bn_ws, p.tile8, p.gridx, stream);
         return;
     case FWD_TILE4:
         break;
@@ -485,10 +486,10 @@ extern "C" void launch_conv_fwd_splitk(const void* x, const void* w, void* ws,
     // same Python-decided spz/zeff and ws layout, deeper pipeline
     if (d.C % 64 == 0 && d.K % 64 == 0 && rsc % 64 == 0 &&
         (int64_t)d.N * d.H * d.W * d.C * 2 < (int64_t)kOobSentinel) {
-        const int mtiles = (int)((M + 255) / 256);
-        const int bn8 = d.K % 128 == 0 ? 128 : 64;
-        if ((int64_t)mtiles * (d.K / bn8) * zeff >= 120) {
-            launch_conv_fwd8_splitk(x, w, ws, d, bn8, mtiles, spz, zeff,
+        const Tile8 t = splitk_tile8(M, d.K);
+        if (blocks8(M, d.K, t) * zeff >= kSplitkFloor8) {
+            launch_conv_fwd8_splitk(x, w, ws, d, t,
+                                    (int)((M + t.bm - 1) / t.bm), spz, zeff,
                                     stream);
             return;
         }

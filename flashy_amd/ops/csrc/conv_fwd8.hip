@@ -2,7 +2,9 @@
 // 8-wave 256-row implicit-GEMM conv FORWARD for gfx950 — the deep-pipeline
 // schedule (CDNA4 guide §5 "256² 8-phase template" adapted to conv):
 //
-//   * 512 threads (8 waves, 2M x 4N), tile BM=256 x BN in {64,128}, BK=64;
+//   * 512 threads (8 waves, 2M x 4N), tile BM in {256,128} x BN in
+//     {64,128}, BK=64 (the 128-row tile: half the m-fragments and A DMA,
+//     4 LDS buffers; the tile plan in conv8.h says which shapes take it);
 //   * BOTH operands staged to LDS by async global->LDS DMA
 //     (`raw_ptr_buffer_load_lds` 16 B/lane): no staging registers, no
 //     ds_write pass, and the A (im2col) padding is handled by the buffer
@@ -23,22 +25,24 @@
 
 #include "conv8.h"
 
-template <int BN, bool RELU, bool SPLITK = false>
+template <int BN, bool RELU, bool SPLITK = false, int BM = 256>
 __global__ void __launch_bounds__(512, 2)
 k_conv_fwd8(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
             uint16_t* __restrict__ y, float* __restrict__ bn_ws,
             ConvDims d, unsigned x_nbytes, int spz = 0) {
-    constexpr int BM = 256;
+    static_assert(BM == 256 || BM == 128, "8 waves as 2(M) x 4(N)");
     constexpr int BK = 64;
     constexpr int NF = BN / 64;          // n fragments per wave (4 N-waves)
-    constexpr int MF = 8;                // m fragments per wave (2 M-waves)
-    constexpr int A_ELEMS = BM * BK;     // 16384 bf16 = 32 KiB
+    constexpr int MF = BM / 32;          // m fragments per wave (2 M-waves)
+    constexpr int AG = BM / 64;          // A glds per wave per stage
+    constexpr int A_ELEMS = BM * BK;     // 16384/8192 bf16 = 32/16 KiB
     constexpr int B_ELEMS = BN * BK;     // 4096/8192 bf16 = 8/16 KiB
     constexpr int BUF_ELEMS = A_ELEMS + B_ELEMS;
-    constexpr int G = 4 + BN / 64;       // glds per wave per stage (A + B)
-    // BN=64 buffers fit 4x in the 160 KiB LDS -> prefetch DEPTH 2 (two
-    // stages' DMA in flight across barriers); BN=128 fits 3 -> depth 1
-    constexpr int BUFS = BN == 64 ? 4 : 3;
+    constexpr int G = AG + BN / 64;      // glds per wave per stage (A + B)
+    // BM=256: BN=64 buffers fit 4x in the 160 KiB LDS -> prefetch DEPTH 2
+    // (two stages' DMA in flight across barriers); BN=128 fits 3 -> depth 1.
+    // BM=128 buffers are 24 / 32 KiB: 4 of them (96 / 128 KiB), depth 2
+    constexpr int BUFS = (BN == 64 || BM == 128) ? 4 : 3;
     constexpr int DEPTH = BUFS - 2;
 
     const int rsc = d.R * d.S * d.C;
@@ -60,13 +64,13 @@ k_conv_fwd8(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
     const auto xrsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)x, 0 /*stride*/, x_nbytes, 0x00020000 /*flags*/);
 
-    // --- A staging state: 4 dest chunks per thread, geometry fixed, tap
+    // --- A staging state: AG dest chunks per thread, geometry fixed, tap
     // (r,s,c) walks +BK per stage with carries (no divides steady-state).
-    int a_r[4], a_s[4], a_c[4], a_hi0[4], a_wi0[4];
-    int64_t a_n[4];
+    int a_r[AG], a_s[AG], a_c[AG], a_hi0[AG], a_wi0[AG];
+    int64_t a_n[AG];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int chunk = g * 512 + tid;          // dest chunk 0..2047
+    for (int g = 0; g < AG; ++g) {
+        const int chunk = g * 512 + tid;          // dest chunk 0..BM*8-1
         const int row = chunk >> 3;
         const int kc_s = (chunk & 7) ^ (row & 7); // source k-chunk (swizzle)
         const int64_t m = m0 + row;
@@ -100,7 +104,7 @@ k_conv_fwd8(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
     auto issue_stage = [&](int stage, int buf) {
         uint16_t* base = lds + buf * BUF_ELEMS;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
+        for (int g = 0; g < AG; ++g) {
             unsigned voff = kOobSentinel;
             if (a_n[g] >= 0 && a_r[g] < d.R) {
                 const int hi = a_hi0[g] + a_r[g];
@@ -136,7 +140,7 @@ k_conv_fwd8(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
     };
 
     // fragment LDS byte offsets (swizzled), fixed per lane
-    const int a_row_l = wave_m * 128 + (lane & 15);   // + mf*16
+    const int a_row_l = wave_m * (BM / 2) + (lane & 15);   // + mf*16
     const int frag_kb = (lane >> 4) * 16;             // byte within 64B half
     const int b_col_l = wave_n * (BN / 4) + (lane & 15);  // + nf*16
 
@@ -212,7 +216,7 @@ k_conv_fwd8(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
     // Swapped-operand D layout: lane l of acc[mf][nf] holds pixel row
     // (mf*16 + (l&15)) at output channels (nf*16 + (l>>4)*4 + rr) — four
     // CONSECUTIVE channels per lane, packed into one 8 B store.
-    const int64_t out_row0 = m0 + wave_m * 128 + (lane & 15);
+    const int64_t out_row0 = m0 + wave_m * (BM / 2) + (lane & 15);
     const int out_col0 = col0 + wave_n * (BN / 4) + (lane >> 4) * 4;
     if (SPLITK) {   // fp32 partials slab [z][M][K], float4 per lane
         float* ws = reinterpret_cast<float*>(bn_ws);   // reused arg
@@ -601,41 +605,77 @@ extern "C" void launch_stem_unpad_dw(const void* dwp, void* dw, int K, int R,
 }
 
 // --- fwd8 plan + launchers ----------------------------------------------------
-extern "C" int conv_fwd8_plan(ConvDims d, int* bn_out) {
-    if (conv8_disabled()) return 0;
-    const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
+// What every fwd8 route needs of the dims (32-bit voffset included)
+static bool fwd8_can_run(ConvDims d) {
     const int rsc = d.R * d.S * d.C;
-    if (d.C % 64 || d.K % 64 || rsc % 64) return 0;
+    if (d.C % 64 || d.K % 64 || rsc % 64) return false;
     const int64_t x_elems = (int64_t)d.N * d.H * d.W * d.C;
-    if (x_elems * 2 >= (int64_t)kOobSentinel) return 0;   // 32-bit voffset
-    const int mtiles = (int)((M + 255) / 256);
-    return pick_bn8(mtiles, d.K, 160, bn_out) ? mtiles : 0;
+    return x_elems * 2 < (int64_t)kOobSentinel;
+}
+
+extern "C" int conv_fwd8_plan(ConvDims d, Tile8* tile_out) {
+    if (conv8_disabled() || !fwd8_can_run(d)) return 0;
+    const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
+    if (!pick_tile8(M, d.K, kFloor8, tile_out)) return 0;
+    return (int)((M + tile_out->bm - 1) / tile_out->bm);
 }
 
 extern "C" void launch_conv_fwd8(const void* x, const void* w, void* y,
-                                 ConvDims d, int relu, void* bn_ws, int bn,
-                                 int mtiles, hipStream_t stream) {
-    dim3 grid((unsigned)mtiles, (unsigned)(d.K / bn));
+                                 ConvDims d, int relu, void* bn_ws,
+                                 Tile8 tile, int mtiles, hipStream_t stream) {
+    dim3 grid((unsigned)mtiles, (unsigned)(d.K / tile.bn));
     const unsigned xb = (unsigned)((int64_t)d.N * d.H * d.W * d.C * 2);
-    dispatch8(bn, relu, [&](auto BN, auto RELU) {
-        k_conv_fwd8<decltype(BN)::value, decltype(RELU)::value>
+    dispatch8(tile, relu, [&](auto BM, auto BN, auto RELU) {
+        k_conv_fwd8<decltype(BN)::value, decltype(RELU)::value, false,
+                    decltype(BM)::value>
             <<<grid, 512, 0, stream>>>((const uint16_t*)x, (const uint16_t*)w,
                                        (uint16_t*)y, (float*)bn_ws, d, xb);
     });
 }
 
 extern "C" void launch_conv_fwd8_splitk(const void* x, const void* w,
-                                        void* ws, ConvDims d, int bn,
+                                        void* ws, ConvDims d, Tile8 tile,
                                         int mtiles, int spz, int zeff,
                                         hipStream_t stream) {
-    dim3 grid((unsigned)mtiles, (unsigned)(d.K / bn), (unsigned)zeff);
+    dim3 grid((unsigned)mtiles, (unsigned)(d.K / tile.bn), (unsigned)zeff);
     const unsigned xb = (unsigned)((int64_t)d.N * d.H * d.W * d.C * 2);
-    auto xx = (const uint16_t*)x;
-    auto ww = (const uint16_t*)w;
-    if (bn == 128)
-        k_conv_fwd8<128, false, true><<<grid, 512, 0, stream>>>(
-            xx, ww, nullptr, (float*)ws, d, xb, spz);
-    else
-        k_conv_fwd8<64, false, true><<<grid, 512, 0, stream>>>(
-            xx, ww, nullptr, (float*)ws, d, xb, spz);
+    dispatch8(tile, false, [&](auto BM, auto BN, auto) {
+        k_conv_fwd8<decltype(BN)::value, false, true, decltype(BM)::value>
+            <<<grid, 512, 0, stream>>>((const uint16_t*)x, (const uint16_t*)w,
+                                       nullptr, (float*)ws, d, xb, spz);
+    });
+}
+
+static bool tile8_ok(Tile8 t, int channels) {
+    return (t.bm == 256 || t.bm == 128) && (t.bn == 128 || t.bn == 64) &&
+           channels % t.bn == 0;
+}
+
+extern "C" int launch_conv8_form(int dgrad, const void* a, const void* w,
+                                 void* out, void* bn_ws, ConvDims d,
+                                 Tile8 tile, int spz, hipStream_t stream) {
+    if (spz < 0 || !tile8_ok(tile, dgrad ? d.C : d.K)) return 0;
+    const int64_t M = dgrad ? (int64_t)d.N * d.H * d.W
+                            : (int64_t)d.N * d.Ho * d.Wo;
+    const int mtiles = (int)((M + tile.bm - 1) / tile.bm);
+    const int stages = d.R * d.S * (dgrad ? d.K : d.C) / 64;
+    const int zeff = spz ? (stages + spz - 1) / spz : 1;
+    if (dgrad) {
+        ConvDims f = d;   // the dgrad GEMM reads dout: same limits, K <-> C
+        f.C = d.K; f.K = d.C; f.H = d.Ho; f.W = d.Wo;
+        if (!fwd8_can_run(f)) return 0;
+        if (spz)
+            launch_conv_dgrad8_splitk(a, w, out, d, tile, mtiles, spz, zeff,
+                                      stream);
+        else
+            launch_conv_dgrad8(a, w, out, d, tile, mtiles, stream);
+        return 1;
+    }
+    if (!fwd8_can_run(d)) return 0;
+    if (spz) {
+        launch_conv_fwd8_splitk(a, w, out, d, tile, mtiles, spz, zeff, stream);
+        return 1;
+    }
+    launch_conv_fwd8(a, w, out, d, 0, bn_ws, tile, mtiles, stream);
+    return mtiles;
 }

@@ -299,7 +299,7 @@ PYBIND11_MODULE(_hip_ops, m) {
               launch_conv_fwd8((const void*)x, (const void*)w, (void*)y,
                                make_dims(N, H, W, C, K, R, S, Ho, Wo, stride,
                                          pad),
-                               relu, (void*)bn_ws, bn, mtiles,
+                               relu, (void*)bn_ws, Tile8{256, bn}, mtiles,
                                as_stream(stream));
               check_last();
           });
@@ -331,10 +331,46 @@ PYBIND11_MODULE(_hip_ops, m) {
     m.def("conv8_eligible",
           [](int N, int H, int W, int C, int K, int R, int S, int Ho, int Wo,
              int stride, int pad, bool dgrad) {
-              int bn = 0;
+              Tile8 t = {};
               ConvDims d = make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad);
-              return (dgrad ? conv_dgrad8_plan(d, &bn)
-                            : conv_fwd8_plan(d, &bn)) > 0;
+              return (dgrad ? conv_dgrad8_plan(d, &t)
+                            : conv_fwd8_plan(d, &t)) > 0;
+          });
+    // the single-pass 8-wave plan as (bm, bn, grid.x); zeros = not eligible
+    m.def("conv8_plan",
+          [](int N, int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad, bool dgrad) {
+              Tile8 t = {};
+              ConvDims d = make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad);
+              const int mt = dgrad ? conv_dgrad8_plan(d, &t)
+                                   : conv_fwd8_plan(d, &t);
+              if (!mt) t = Tile8{0, 0};
+              return py::make_tuple(t.bm, t.bn, mt);
+          });
+    // the split-K tile for `rows` GEMM rows and `channels` columns, and the
+    // rows per block the split factor is sized with: (bm, bn, sizing_rows)
+    m.def("conv8_splitk_tile", [](int64_t rows, int channels) {
+        if (rows <= 0 || channels <= 0 || channels % 64)
+            throw std::invalid_argument("conv8_splitk_tile: bad extent");
+        const Tile8 t = splitk_tile8(rows, channels);
+        return py::make_tuple(t.bm, t.bn, kSplitSizingRows);
+    });
+    // one 8-wave kernel by name (tests, scripts/splitk_sweep.py)
+    m.def("conv8_form",
+          [](bool dgrad, uintptr_t a, uintptr_t w, uintptr_t out,
+             uintptr_t bn_ws, int N, int H, int W, int C, int K, int R, int S,
+             int Ho, int Wo, int stride, int pad, int bm, int bn, int spz,
+             uintptr_t stream) {
+              const int r = launch_conv8_form(
+                  dgrad ? 1 : 0, (const void*)a, (const void*)w, (void*)out,
+                  (void*)bn_ws,
+                  make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                  Tile8{bm, bn}, spz, as_stream(stream));
+              if (!r)
+                  throw std::invalid_argument(
+                      "conv8_form: tile cannot run this shape");
+              check_last();
+              return r;
           });
 
     m.def("conv_fwd_msplit",

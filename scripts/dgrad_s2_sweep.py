@@ -98,6 +98,7 @@ def run_shape(name):
            f"current[{plan}] "
            f"{time_us(lambda: ops.conv_dgrad(dy, wt, dx, d)):.1f}"]
     forms = [("generic", 0), ("par8", 64), ("par8", 128),
+             ("par8m128", 64), ("par8m128", 128),
              ("par4", 128), ("par4", 64), ("par4", 32)]
     if R == 1:
         forms += [("scat2", 64), ("scat2", 128)]
