@@ -903,6 +903,30 @@ def weight_transpose(w: torch.Tensor, wt: torch.Tensor) -> None:
     ext.weight_transpose(w.data_ptr(), wt.data_ptr(), K, rsc, _stream())
 
 
+def _wgrad_splits(d: ConvDims) -> int:
+    forced = os.environ.get("FLASHY_WGRAD_SPLITS")
+    if forced:  # e.g. =1 -> deterministic wgrad (no atomic splits)
+        return int(forced)
+    tiles = (d.K // 64) * (d.R * d.S * d.C // 64)
+    n_splits = max(1, min(1024 // tiles if tiles else 1, 128))
+    M = d.N * d.Ho * d.Wo
+    return max(1, min(n_splits, M // 32 or 1))
+
+
+def conv_wgrad_form(d: ConvDims, n_splits: tp.Optional[int] = None) -> str:
+    """Name of the kernel `conv_wgrad` runs for (d, n_splits), C % 8 == 0
+    shapes: ``wgrad8``, ``wgrad<MG>`` or ``wgrad_dma<MG,BUFS>``.  The
+    pins FLASHY_WGRAD_MG and FLASHY_WGRAD_DMA (0 = register-staged kernel, 1 =
+    DMA-staged, unset = the launcher's rule) are read on every call."""
+    assert d.C % 8 == 0 and d.K % 64 == 0 and d.R * d.S * d.C % 64 == 0, d
+    if n_splits is None:
+        n_splits = _wgrad_splits(d)
+    kind, mg, bufs, rows = require().conv_wgrad_plan(*d, n_splits)
+    if kind == 2:
+        return "wgrad8"
+    return f"wgrad_dma<{mg},{bufs}>" if kind == 1 else f"wgrad<{mg}>"
+
+
 def conv_wgrad(x: torch.Tensor, dout: torch.Tensor, dw: torch.Tensor,
                d: ConvDims, n_splits: tp.Optional[int] = None) -> None:
     """Accumulates (+=) fp32 weight grads; dw must be zeroed or hold the
@@ -912,14 +936,7 @@ def conv_wgrad(x: torch.Tensor, dout: torch.Tensor, dw: torch.Tensor,
     if d.C % 8 == 0:
         assert d.K % 64 == 0 and rsc % 64 == 0, d
         if n_splits is None:
-            forced = os.environ.get("FLASHY_WGRAD_SPLITS")
-            if forced:  # e.g. =1 -> deterministic wgrad (no atomic splits)
-                n_splits = int(forced)
-            else:
-                tiles = (d.K // 64) * (rsc // 64)
-                n_splits = max(1, min(1024 // tiles if tiles else 1, 128))
-                M = d.N * d.Ho * d.Wo
-                n_splits = max(1, min(n_splits, M // 32 or 1))
+            n_splits = _wgrad_splits(d)
         ext.conv_wgrad(x.data_ptr(), dout.data_ptr(), dw.data_ptr(), *d,
                        n_splits, _stream())
     else:

@@ -442,6 +442,266 @@ k_conv_wgrad8(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dout,
             }
 }
 
+// ---------------------------------------------------------------------------
+// k_conv_wgrad_dma<MG, BUFS>: the 64x64 kernel above with the 8-wave
+// family's stage pipeline.  Decomposition, stage and subchunk order, MFMA
+// shape and operand roles, group-sum order and the adds are those of
+// k_conv_wgrad<MG>, so a tile with one adder block is bitwise what that
+// kernel produces; only how a stage reaches LDS differs:
+//
+//   * both operands go global -> LDS by `buffer_load_lds`, 16 B per lane: no
+//     staging registers and no ds_write.  Rows at or past the range end `me`
+//     (so every row of an empty group) and out-of-image taps take
+//     kOobSentinel as their offset and the descriptor's bounds check writes
+//     zeros; no load can leave x or dout whatever the offsets are;
+//   * a stage is 32 m-rows (one MFMA-K subchunk) of 128 B per operand, 8 KiB
+//     per group; BUFS buffers per wave group, prefetch DEPTH = BUFS - 2 (a
+//     leading wave's next issue then targets buffer (i-1) % BUFS, which every
+//     wave left before barrier i), ONE raw s_barrier per stage behind a
+//     counted `s_waitcnt vmcnt(DEPTH*G)` (G = 2 DMAs per wave per stage); the
+//     last DEPTH+1 stages are peeled, so the steady loop has no vmcnt(0).
+//     All groups run group 0's stage count, as above.  64-row stages (two
+//     subchunks, half the barriers) were built too, with 3 and 4 buffers:
+//     48 / 64 KiB per group hold 3 / 2 groups per CU and MG = 4 does not fit;
+//     four resident groups of 32-row stages won (profiles/README.md, r09a);
+//   * LDS image: dest 16 B chunk t of row m holds source chunk t ^ key(m),
+//     key(m) = (m & 7) ^ ((m >> 1) & 4).  A 16-lane group of
+//     ds_read_b64_tr_b16 reads rows r..r+3 (r % 4 == 0), two chunks per row:
+//     rows r, r+2 start at bank 0 and r+1, r+3 at bank 32 (128 B rows, 64
+//     banks), and the keys of r and r+2 differ in bit 1, so the group's 32
+//     B-per-row pieces land on 32 distinct banks (even rows in 0..31, odd
+//     rows in 32..63).  The next group's rows r+8..r+11 have the same row
+//     phase but keys that differ in bit 2 (the folded row bit 3): the two
+//     groups of a 32-lane half cover each of the 64 banks once.  Each lane
+//     undoes the swizzle in its own address; an 8 B read stays inside one
+//     16 B chunk.
+// Requires what k_conv_wgrad does, and x, dout below 2^31 - 2^28 bytes (32-bit
+// buffer offsets under the sentinel).
+// ---------------------------------------------------------------------------
+
+#include "conv8.h"
+
+template <int MG, int BUFS>
+__global__ void __launch_bounds__(CONV_THREADS * MG)
+k_conv_wgrad_dma(const uint16_t* __restrict__ x,
+                 const uint16_t* __restrict__ dout, float* __restrict__ dw,
+                 ConvDims d, int m_per_split, int single, unsigned x_nbytes,
+                 unsigned dout_nbytes) {
+    static_assert(BUFS >= 3, "prefetch depth BUFS - 2");
+    constexpr int DEPTH = BUFS - 2;
+    constexpr int SR = CONV_BK;                // m rows per stage
+    constexpr int G = 2;                       // DMAs per wave per stage
+    constexpr int OP_BYTES = SR * 128;         // one operand's stage image
+    constexpr int BUF_BYTES = 2 * OP_BYTES;    // dout + x
+    constexpr int GROUP_BYTES = BUFS * BUF_BYTES;
+    static_assert(GROUP_BYTES >= 64 * WG_TP * 4, "epilogue tile fits a group");
+
+    const int rsc = d.R * d.S * d.C;
+    const int M = d.N * d.Ho * d.Wo;
+    const int wid_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = wid_u >> 2;                   // wave group
+    const int wid = wid_u & 3;                    // wave within the group
+    const int tid = threadIdx.x % CONV_THREADS;   // thread within the group
+    const int lane = tid & 63;
+    const int wave_k = wid >> 1;   // K halves (32 rows each)
+    const int wave_j = wid & 1;    // rsc halves
+    const int k0 = blockIdx.x * 64;
+    const int j0 = blockIdx.y * 64;
+    const int64_t ms0 = (int64_t)blockIdx.z * MG * m_per_split;   // < M
+    const int ms = (int)min(ms0 + (int64_t)grp * m_per_split, (int64_t)M);
+    const int me = (int)min((int64_t)ms + m_per_split, (int64_t)M);
+
+    // per group: BUFS x [dout SR rows][x SR rows], 128 B rows
+    extern __shared__ __attribute__((aligned(16))) uint16_t wg_lds[];
+    char* const gbase = reinterpret_cast<char*>(wg_lds) + grp * GROUP_BYTES;
+
+    const auto xrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)x, 0 /*stride*/, x_nbytes, 0x00020000 /*flags*/);
+    const auto drsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)dout, 0, dout_nbytes, 0x00020000);
+
+    floatx4 acc[2][2] = {};
+
+    // staging: thread -> dest chunk (tid & 7) of stage row (tid >> 3); the
+    // row's key is the same in every stage (+32 rows), so the source chunk
+    // and with it the im2col tap are fixed per thread.
+    const int m_r = tid >> 3;                                 // 0..31
+    const int k8 = ((tid & 7) ^ (m_r & 7) ^ ((m_r >> 1) & 4)) * 8;
+    const int t_r = (j0 + k8) / (d.S * d.C);
+    const int t_scc = (j0 + k8) - t_r * d.S * d.C;
+    const int t_s = t_scc / d.C;
+    const int t_c = t_scc - t_s * d.C;
+    const int t_hoff = t_r - d.pad;      // hi = ho*stride + t_hoff
+    const int t_woff = t_s - d.pad;
+    // the row's m and its (n, ho, wo), walked +SR per stage with one carry
+    // each (SR = s_n*Ho*Wo + s_h*Wo + s_w): no divides in the loop
+    const int hw = d.Ho * d.Wo;
+    const int s_n = SR / hw;
+    const int s_h = (SR - s_n * hw) / d.Wo;
+    const int s_w = SR - s_n * hw - s_h * d.Wo;
+    int r_m = ms + m_r;
+    int r_n = r_m / hw;
+    int r_ho = (r_m - r_n * hw) / d.Wo;
+    int r_wo = r_m - r_n * hw - r_ho * d.Wo;
+    unsigned r_doff = (unsigned)(((int64_t)r_m * d.K + k0 + k8) * 2);
+    const unsigned doff_step = (unsigned)(SR * d.K * 2);
+
+    auto issue_stage = [&](int buf) {
+        char* const base = gbase + buf * BUF_BYTES;
+        unsigned dvo = kOobSentinel, xvo = kOobSentinel;
+        if (r_m < me) {
+            dvo = r_doff;
+            const int hi = r_ho * d.stride + t_hoff;
+            const int wi = r_wo * d.stride + t_woff;
+            if (hi >= 0 && hi < d.H && wi >= 0 && wi < d.W)
+                xvo = (unsigned)((((r_n * d.H + hi) * d.W + wi) * d.C + t_c) *
+                                 2);
+        }
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            drsrc,
+            (__attribute__((address_space(3))) void*)(base + wid * 64 * 16),
+            16, dvo, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            xrsrc,
+            (__attribute__((address_space(3))) void*)
+                (base + OP_BYTES + wid * 64 * 16),
+            16, xvo, 0, 0, 0);
+        // advance the row by one stage
+        r_m += SR;
+        r_doff += doff_step;
+        r_wo += s_w;
+        if (r_wo >= d.Wo) { r_wo -= d.Wo; ++r_ho; }
+        r_ho += s_h;
+        if (r_ho >= d.Ho) { r_ho -= d.Ho; ++r_n; }
+        r_n += s_n;
+    };
+
+    // tr-read gather (see k_conv_wgrad): group (lane>>4) covers m rows
+    // g*8..g*8+7 in two reads (+4 rows), input lane (lane&15) supplies row
+    // (k>>2), channels ch0 + 4*(k&3).  Swizzled byte offsets per (fragment,
+    // row half).
+    const int tr_row = (lane >> 4) * 8 + ((lane >> 2) & 3);
+    const int tr_key = ((lane >> 2) & 3) ^ (((lane >> 4) & 1) << 2);
+    unsigned a_off[2][2], b_off[2][2];   // [frag][row half]
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int row = tr_row + 4 * h;
+            const int key = tr_key ^ (4 * h);
+            const int sub = ((lane & 3) >> 1);
+            a_off[f][h] = row * 128 + (((wave_k * 4 + f * 2 + sub) ^ key) << 4) +
+                          (lane & 1) * 8;
+            b_off[f][h] = OP_BYTES + row * 128 +
+                          (((wave_j * 4 + f * 2 + sub) ^ key) << 4) +
+                          (lane & 1) * 8;
+        }
+    const unsigned lds_u = (unsigned)(unsigned long long)(const void*)gbase;
+    union U64x2 { struct { unsigned long long lo, hi; } q; short8 v; };
+
+    // one subchunk: 8 transpose reads, 4 MFMAs; the other waves' stages and
+    // the resident groups cover the wait
+    auto compute_stage = [&](int buf) {
+        const unsigned sb = lds_u + buf * BUF_BYTES;
+        U64x2 af[2], bf[2];   // [frag]
+        asm volatile(
+            "ds_read_b64_tr_b16 %0, %8\n\t"
+            "ds_read_b64_tr_b16 %1, %9\n\t"
+            "ds_read_b64_tr_b16 %2, %10\n\t"
+            "ds_read_b64_tr_b16 %3, %11\n\t"
+            "ds_read_b64_tr_b16 %4, %12\n\t"
+            "ds_read_b64_tr_b16 %5, %13\n\t"
+            "ds_read_b64_tr_b16 %6, %14\n\t"
+            "ds_read_b64_tr_b16 %7, %15\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(af[0].q.lo), "=&v"(af[0].q.hi),
+              "=&v"(af[1].q.lo), "=&v"(af[1].q.hi),
+              "=&v"(bf[0].q.lo), "=&v"(bf[0].q.hi),
+              "=&v"(bf[1].q.lo), "=&v"(bf[1].q.hi)
+            : "v"(sb + a_off[0][0]), "v"(sb + a_off[0][1]),
+              "v"(sb + a_off[1][0]), "v"(sb + a_off[1][1]),
+              "v"(sb + b_off[0][0]), "v"(sb + b_off[0][1]),
+              "v"(sb + b_off[1][0]), "v"(sb + b_off[1][1])
+            : "memory");
+#pragma unroll
+        for (int kf = 0; kf < 2; ++kf)
+#pragma unroll
+            for (int jf = 0; jf < 2; ++jf)
+                acc[kf][jf] = MFMA_BF16(af[kf].v, bf[jf].v, acc[kf][jf]);
+        // no tail barrier: the next stage's barrier bounds the wave skew
+    };
+
+    // block-uniform: group 0's stage count.  k_conv_wgrad counts 64-row
+    // stages; each is two of these, so the zero subchunk past a range's end
+    // is multiplied exactly as there.
+    const int n_stages =
+        (int)((min(ms0 + (int64_t)m_per_split, (int64_t)M) - ms0 +
+               2 * CONV_BK - 1) / (2 * CONV_BK)) * 2;
+
+    for (int p = 0; p < DEPTH && p < n_stages; ++p) issue_stage(p % BUFS);
+    for (int i = 0; i + DEPTH < n_stages; ++i) {
+        issue_stage((i + DEPTH) % BUFS);
+        // stage i landed; the DEPTH later stages' DMA stays in flight
+        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(DEPTH * G) : "memory");
+        __builtin_amdgcn_s_barrier();
+        compute_stage(i % BUFS);
+    }
+#pragma unroll
+    for (int t = DEPTH - 1; t >= 1; --t)     // tail, t stages still in flight
+        if (n_stages > t) {
+            if (t == 2)
+                asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * G) : "memory");
+            else
+                asm volatile("s_waitcnt vmcnt(%0)" ::"i"(G) : "memory");
+            __builtin_amdgcn_s_barrier();
+            compute_stage((n_stages - 1 - t) % BUFS);
+        }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    compute_stage((n_stages - 1) % BUFS);
+
+    // ---- accumulate into fp32 dw: k_conv_wgrad's epilogue ----------------
+    const int t_k = wave_k * 32 + (lane >> 4) * 4;
+    const int t_j = wave_j * 32 + (lane & 15);
+    if constexpr (MG == 1) {
+        if (!single) {
+#pragma unroll
+            for (int kf = 0; kf < 2; ++kf)
+#pragma unroll
+                for (int jf = 0; jf < 2; ++jf)
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr)
+                        atomicAdd(&dw[(int64_t)(k0 + t_k + kf * 16 + rr) * rsc +
+                                      j0 + t_j + jf * 16],
+                                  acc[kf][jf][rr]);
+            return;
+        }
+    }
+    __syncthreads();   // every wave is past its last stage's reads
+    float* const tile = reinterpret_cast<float*>(gbase);   // [64][WG_TP]
+#pragma unroll
+    for (int kf = 0; kf < 2; ++kf)
+#pragma unroll
+        for (int jf = 0; jf < 2; ++jf)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr)
+                tile[(t_k + kf * 16 + rr) * WG_TP + t_j + jf * 16] =
+                    acc[kf][jf][rr];
+    __syncthreads();
+    const float* const tiles = reinterpret_cast<const float*>(wg_lds);
+    for (int r = threadIdx.x >> 6; r < 64; r += 4 * MG) {
+        float v = tiles[r * WG_TP + lane];
+#pragma unroll
+        for (int g = 1; g < MG; ++g)
+            v += tiles[g * (GROUP_BYTES / 4) + r * WG_TP + lane];
+        float* const p = &dw[(int64_t)(k0 + r) * rsc + j0 + lane];
+        if (single)
+            *p += v;
+        else
+            atomicAdd(p, v);
+    }
+}
+
 #include <cstdlib>
 // FLASHY_WGRAD_MG=1|2|4 pins the wave-group count of k_conv_wgrad (read on
 // every call: scripts/wgrad_sweep.py and the tests flip it in-process).
@@ -507,21 +767,105 @@ static void launch_wgrad_mg(const void* x, const void* dout, void* dw,
         zn == 1);
 }
 
+// 128x128 tile only where re-read traffic dominates (R*S > 1): the 1x1
+// wgrads already run at the HBM roof on the 64x64 kernel's 4-blocks/CU
+// occupancy, and the 1-block/CU 8-wave kernel loses TLP there (measured:
+// 1x1 196->156 TF, 3x3 186->244 TF).  Within 3x3, the measured win/loss
+// split over the ResNet-50/224 + CIFAR shapes: big M always wins, small
+// M only with enough (K,rsc) tiles to fill the chip.
+static bool wgrad_uses_wg8(const ConvDims& d) {
+    const int rsc = d.R * d.S * d.C;
+    const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
+    const int tiles8 = (d.K / 128) * (rsc / 128);
+    return d.R * d.S > 1 && d.K % 128 == 0 && rsc % 128 == 0 &&
+           (M >= 32768 || (M >= 8192 && tiles8 >= 18) || tiles8 >= 100);
+}
+
+// FLASHY_WGRAD_DMA=0|1 pins k_conv_wgrad (0) or k_conv_wgrad_dma (1) for the
+// 64x64 tile, read on every call like FLASHY_WGRAD_MG; unset = the rule.
+static int wgrad_dma_forced() {
+    const char* e = getenv("FLASHY_WGRAD_DMA");
+    if (e && (e[0] == '0' || e[0] == '1') && !e[1]) return e[0] - '0';
+    return -1;
+}
+
+constexpr int kWgradDmaBufs = 4;   // x 8 KiB stages = 32 KiB per wave group
+
+// The 64x64 tile's dispatch for (d, n_splits): ranges, wave groups, and which
+// pipeline stages them.
+struct WgradPlan {
+    int m_per_split, ranges, mg;
+    bool dma;
+};
+
+// Sizes the DMA kernel's 32-bit buffer offsets allow (conv8.h).
+static bool wgrad_dma_can(const ConvDims& d) {
+    const int64_t lim = ((int64_t)1 << 31) - ((int64_t)1 << 28);
+    const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
+    // C % 8: a 16 B chunk is one tap (the padded stem's C = 4 stays out)
+    return d.C % 8 == 0 && (int64_t)d.N * d.H * d.W * d.C * 2 < lim &&
+           M * d.K * 2 < lim;
+}
+
+// Which shapes the DMA pipeline takes, from the dims alone (sweep in
+// profiles/README.md, r09a, at the MG and ranges of wgrad_pick_mg, which stay
+// as they are): every k x k shape of the 64x64 tile (-17% to -42% on the
+// flagship's six, -1.5% on the ResNet-50/224 64->64 3x3), and 1x1 shapes
+// whose ranges run at least two 64-row stages (-6% on the 32x32 64->128
+// stride-2 downsample, -11% on the ResNet-50 64->256).  A 1x1 range of one
+// stage is all fill and epilogue: the 128->256 and 256->512 downsamples
+// measured 0.1-0.4 us apart, inside what two passes differ by, and stay.
+static bool wgrad_dma_rule(const ConvDims& d, int m_per_split) {
+    return d.R * d.S > 1 || m_per_split >= 4 * CONV_BK;
+}
+
+static WgradPlan wgrad_plan64(const ConvDims& d, int n_splits) {
+    const int rsc = d.R * d.S * d.C;
+    const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
+    WgradPlan p;
+    p.m_per_split = (int)((M + n_splits - 1) / n_splits);
+    p.m_per_split =
+        (p.m_per_split + 2 * CONV_BK - 1) / (2 * CONV_BK) * (2 * CONV_BK);
+    p.ranges = (int)((M + p.m_per_split - 1) / p.m_per_split);
+    const int tiles = (d.K / 64) * (rsc / 64);
+    p.mg = wgrad_mg_forced();
+    if (!p.mg) p.mg = wgrad_pick_mg(tiles, p.ranges, p.m_per_split);
+    const int pin = wgrad_dma_forced();
+    p.dma = wgrad_dma_can(d) &&
+            (pin >= 0 ? pin == 1 : wgrad_dma_rule(d, p.m_per_split));
+    return p;
+}
+
+template <int MG>
+static void launch_wgrad_dma(const void* x, const void* dout, void* dw,
+                             const ConvDims& d, const WgradPlan& p,
+                             hipStream_t stream) {
+    // 128 KiB at MG = 4
+    constexpr int lds = MG * kWgradDmaBufs * 2 * CONV_BK * 128;
+    static const bool attr_set = [] {
+        (void)hipFuncSetAttribute(
+            (const void*)&k_conv_wgrad_dma<MG, kWgradDmaBufs>,
+            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        return true;
+    }();
+    (void)attr_set;
+    const int zn = (p.ranges + MG - 1) / MG;
+    const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
+    dim3 grid((unsigned)(d.K / 64), (unsigned)(d.R * d.S * d.C / 64),
+              (unsigned)zn);
+    k_conv_wgrad_dma<MG, kWgradDmaBufs>
+        <<<grid, CONV_THREADS * MG, lds, stream>>>(
+            (const uint16_t*)x, (const uint16_t*)dout, (float*)dw, d,
+            p.m_per_split, zn == 1,
+            (unsigned)((int64_t)d.N * d.H * d.W * d.C * 2),
+            (unsigned)(M * d.K * 2));
+}
+
 extern "C" void launch_conv_wgrad(const void* x, const void* dout, void* dw,
                                   ConvDims d, int n_splits, hipStream_t stream) {
     const int rsc = d.R * d.S * d.C;
     const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
-    // 128x128 tile only where re-read traffic dominates (R*S > 1): the 1x1
-    // wgrads already run at the HBM roof on the 64x64 kernel's 4-blocks/CU
-    // occupancy, and the 1-block/CU 8-wave kernel loses TLP there (measured:
-    // 1x1 196->156 TF, 3x3 186->244 TF).  Within 3x3, the measured win/loss
-    // split over the ResNet-50/224 + CIFAR shapes: big M always wins, small
-    // M only with enough (K,rsc) tiles to fill the chip.
-    const int tiles8 = (d.K / 128) * (rsc / 128);
-    const bool wg8 = d.R * d.S > 1 && d.K % 128 == 0 && rsc % 128 == 0 &&
-                     (M >= 32768 || (M >= 8192 && tiles8 >= 18) ||
-                      tiles8 >= 100);
-    if (wg8) {
+    if (wgrad_uses_wg8(d)) {
         const int tiles = (d.K / 128) * (rsc / 128);
         int ns = n_splits;
         if (ns > 1) {   // re-target for 512-thread blocks (one per CU)
@@ -540,16 +884,36 @@ extern "C" void launch_conv_wgrad(const void* x, const void* dout, void* dw,
             zn == 1);
         return;
     }
-    int m_per_split = (int)((M + n_splits - 1) / n_splits);
-    m_per_split = (m_per_split + 2 * CONV_BK - 1) / (2 * CONV_BK) * (2 * CONV_BK);
-    const int ranges = (int)((M + m_per_split - 1) / m_per_split);
-    const int tiles = (d.K / 64) * (rsc / 64);
-    int mg = wgrad_mg_forced();
-    if (!mg) mg = wgrad_pick_mg(tiles, ranges, m_per_split);
-    if (mg == 4)
-        launch_wgrad_mg<4>(x, dout, dw, d, m_per_split, ranges, stream);
-    else if (mg == 2)
-        launch_wgrad_mg<2>(x, dout, dw, d, m_per_split, ranges, stream);
+    const WgradPlan p = wgrad_plan64(d, n_splits);
+    if (p.dma) {
+        if (p.mg == 4)
+            launch_wgrad_dma<4>(x, dout, dw, d, p, stream);
+        else if (p.mg == 2)
+            launch_wgrad_dma<2>(x, dout, dw, d, p, stream);
+        else
+            launch_wgrad_dma<1>(x, dout, dw, d, p, stream);
+        return;
+    }
+    if (p.mg == 4)
+        launch_wgrad_mg<4>(x, dout, dw, d, p.m_per_split, p.ranges, stream);
+    else if (p.mg == 2)
+        launch_wgrad_mg<2>(x, dout, dw, d, p.m_per_split, p.ranges, stream);
     else
-        launch_wgrad_mg<1>(x, dout, dw, d, m_per_split, ranges, stream);
+        launch_wgrad_mg<1>(x, dout, dw, d, p.m_per_split, p.ranges, stream);
+}
+
+// What launch_conv_wgrad runs for (d, n_splits), pins included: returns 2 for
+// k_conv_wgrad8, 1 for k_conv_wgrad_dma<mg, bufs> (32-row stages), 0 for
+// k_conv_wgrad<mg> (bufs = 2, rows = 64).
+extern "C" int conv_wgrad_plan(ConvDims d, int n_splits, int* mg, int* bufs,
+                               int* rows) {
+    if (wgrad_uses_wg8(d)) {
+        *mg = 1, *bufs = 2, *rows = 64;
+        return 2;
+    }
+    const WgradPlan p = wgrad_plan64(d, n_splits);
+    *mg = p.mg;
+    *bufs = p.dma ? kWgradDmaBufs : 2;
+    *rows = p.dma ? CONV_BK : 64;
+    return p.dma ? 1 : 0;
 }

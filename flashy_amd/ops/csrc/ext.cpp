@@ -58,6 +58,7 @@ void launch_weight_transpose_batched(const void* src, void* dst,
                                      int64_t max_elems, hipStream_t stream);
 void launch_conv_wgrad(const void* x, const void* dout, void* dw, ConvDims d,
                        int n_splits, hipStream_t stream);
+int conv_wgrad_plan(ConvDims d, int n_splits, int* mg, int* bufs, int* rows);
 int gconv_plan(ConvDims d, int groups, int* wgrad_splits);
 void launch_gconv_expand(const void* w16, void* wexp, int K, int Cg, int dgrad,
                          hipStream_t stream);
@@ -496,6 +497,17 @@ PYBIND11_MODULE(_hip_ops, m) {
                                 make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
                                 n_splits, as_stream(stream));
               check_last();
+          });
+    // what conv_wgrad runs for a shape: (kind, MG, buffers, stage rows),
+    // kind 2 = k_conv_wgrad8, 1 = k_conv_wgrad_dma, 0 = k_conv_wgrad
+    m.def("conv_wgrad_plan",
+          [](int N, int H, int W, int C, int K, int R, int S, int Ho, int Wo,
+             int stride, int pad, int n_splits) {
+              int mg = 0, bufs = 0, rows = 0;
+              const int kind = conv_wgrad_plan(
+                  make_dims(N, H, W, C, K, R, S, Ho, Wo, stride, pad),
+                  n_splits, &mg, &bufs, &rows);
+              return py::make_tuple(kind, mg, bufs, rows);
           });
     // grouped 3x3 conv (csrc/conv_group.hip): the plan's (Ci, wgrad splits),
     // Ci = 0 where the grouped path does not serve the shape; the launchers

@@ -1,9 +1,11 @@
 # Time ops.conv_wgrad on the flagship (ResNet-18 CIFAR b64) body/downsample
 # shapes and the ResNet-50/224 shapes.
 #   python scripts/wgrad_sweep.py            per-shape us at the default dispatch
-#   python scripts/wgrad_sweep.py --sweep    block target (n_splits) x MG grid
-# MG is pinned through FLASHY_WGRAD_MG (read by the launcher on every call;
-# builds without wave groups ignore it, so run those without --sweep).
+#   python scripts/wgrad_sweep.py --sweep    block target (n_splits) x MG grid,
+#                                            one row per staging pipeline
+# MG is pinned through FLASHY_WGRAD_MG, the pipeline through FLASHY_WGRAD_DMA
+# (0 = register-staged k_conv_wgrad, 1 = k_conv_wgrad_dma); the launcher reads
+# both on every call.  Shapes that run k_conv_wgrad8 ignore them.
 import os
 import sys
 import torch
@@ -26,6 +28,8 @@ SHAPES = {  # name: (N,H,W,C,K,R,stride)
     "r50-l1c3": (64, 56, 56, 64, 256, 1, 1),
     "r50-l3c2": (64, 14, 14, 256, 256, 3, 1),
 }
+FORMS = {"reg": "0", "dma": "1"}   # pipeline name: FLASHY_WGRAD_DMA
+PINS = ("FLASHY_WGRAD_MG", "FLASHY_WGRAD_DMA")
 ITERS = 50
 
 
@@ -42,6 +46,16 @@ def time_us(fn):
     return s.elapsed_time(e) / ITERS * 1000
 
 
+def pin(mg, form):
+    os.environ["FLASHY_WGRAD_MG"] = str(mg)
+    os.environ["FLASHY_WGRAD_DMA"] = FORMS[form]
+
+
+def unpin():
+    for name in PINS:
+        os.environ.pop(name, None)
+
+
 sweep = "--sweep" in sys.argv
 for name, (N, H, W, C, K, R, st) in SHAPES.items():
     pad = R // 2
@@ -52,16 +66,19 @@ for name, (N, H, W, C, K, R, st) in SHAPES.items():
     dw = torch.zeros(K, R, R, C, device="cuda", dtype=torch.float32)
     tiles = (K // 64) * (R * R * C // 64)
     M = d.N * d.Ho * d.Wo
-    out = [f"{name} M={M} tiles={tiles}:",
-           f"default {time_us(lambda: ops.conv_wgrad(x, dy, dw, d)):.1f}us"]
-    if sweep:
-        for target in (512, 640, 768, 1024, 2048):
+    print(f"{name} M={M} tiles={tiles}: {ops.conv_wgrad_form(d)} default "
+          f"{time_us(lambda: ops.conv_wgrad(x, dy, dw, d)):.1f}us", flush=True)
+    if not sweep or ops.conv_wgrad_form(d) == "wgrad8":
+        continue
+    for form in FORMS:
+        out = [f"  {form:6}"]
+        for target in (512, 768, 1024, 2048):
             ns = max(1, min(target // tiles, 128, M // 32 or 1))
             cell = []
             for mg in (1, 2, 4):
-                os.environ["FLASHY_WGRAD_MG"] = str(mg)
+                pin(mg, form)
                 t = time_us(lambda: ops.conv_wgrad(x, dy, dw, d, n_splits=ns))
+                unpin()
                 cell.append(f"{t:.1f}")
-            os.environ.pop("FLASHY_WGRAD_MG")
-            out.append(f"z{ns} mg1/2/4 " + "/".join(cell))
-    print("  ".join(out), flush=True)
+            out.append(f"z{ns} " + "/".join(cell))
+        print("  ".join(out), flush=True)
